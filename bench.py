@@ -6,10 +6,14 @@ composite]) over one synthetic batch of rays that is already resident in HBM.  D
 configs[1] ("ship_straight": 4096 rays x 128 samples, G=512 grid == 1, flat N_f=0).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--fine F] [--precision P] [--rays B]
+                  [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver through torch.distributed.run (one process per GPU, RCCL).  Rays shard
 embarrassingly (weak scaling, no data-path collective); the only collectives are the timing barrier / max.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline;
+--full adds every other measurement and check (rooflines, legs, variants, frames, collectives, CPU baseline).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (inputs are seeded: same
+arguments, same inputs), so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -232,6 +236,32 @@ def dtype_label(precision, backward, train):
     return (fwd if bwd == fwd else fwd + " fwd, " + bwd + " bwd") + "/fp32-acc"
 
 
+DUMP_BUDGET_BYTES = 60 << 20          # --dump-outputs: the arrays' bytes, kept below 64 MB in all with the .npy headers
+
+
+def dump_outputs(arrays, directory):
+    """Write every array as DIR/<name>.npy in float32 (float64 stays float64).  When they exceed the budget together, the budget is shared
+    out smallest first and an array above its share is replaced by a fixed sample of its rows (seed 0, sorted indices: the same rows in
+    every run)."""
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        host[name] = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+    left = DUMP_BUDGET_BYTES
+    for i, name in enumerate(sorted(host, key=lambda n: host[n].nbytes)):
+        a = host[name]
+        share = left // (len(host) - i)
+        if a.nbytes > share:
+            rows = a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1, 1)
+            k = max(1, share // max(rows.shape[1] * a.itemsize, 1))
+            idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=min(k, rows.shape[0]), replace=False))
+            a = a.reshape(-1)[idx] if a.ndim <= 1 else a[idx]
+        left -= a.nbytes
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def relaunch_for_gpus(args):
     """`--gpus N` is the contract, not a label: one process per GPU.  Started bare (`python bench.py --gpus N`, no launcher in the
     environment) with N > 1, this process becomes the launcher: it starts `python -m torch.distributed.run --nproc-per-node N bench.py
@@ -296,7 +326,8 @@ class Stepper:
         if self.g is not None:
             # the rays of the step after are already in the other static slot (a loader would write them there: GraphTrainStep.next_buffers);
             # their march is a side branch of this step's graph
-            return self.g.step().loss
+            self.last = self.g.step()
+            return self.last.loss
         if self.train:
             from samplenerfro_amd.train import train_step
             nxt = self.rays if (self.pipeline and not last) else None
@@ -313,6 +344,7 @@ class Stepper:
             # the march of step k+1 is issued on the side stream behind the backward of step k
             _, stats, self.rng = train_step(self.model, self.rng, self.tstate, self.batch, self.flags, path=self.h, next_rays=nxt)
             self.h = self.tstate.next_path
+            self.last = stats
             return stats.loss
         m, a = self.model, self.args
         h = self.h if self.pipeline else None
@@ -320,7 +352,27 @@ class Stepper:
             h = m.prefetch_path(self.rays, sync_inputs=False, reserve_cus=a.reserve_cus)
         self.h = m.prefetch_path(self.rays, sync_inputs=False, reserve_cus=a.reserve_cus) if (self.pipeline and not last) else None
         ret, _ = m.apply(self.variables, self.key, self.key, self.rays, False, path=h)
+        self.last = ret
         return ret[-1][0]
+
+    def outputs(self):
+        """What a caller of the timed path holds after the last step: train — the state (parameters, Adam moments, the flat gradient +
+        stats buffer) and the step's Stats; forward — every level's (comp_rgb, distance, acc, trans, trans_rgb_bkgd)."""
+        import dataclasses
+        import torch
+        out = {}
+        if self.train:
+            ts = self.tstate
+            out.update(params=ts.theta, adam_mu=ts.mu, adam_nu=ts.nu, grads=ts.grads)
+            for f in dataclasses.fields(self.last):
+                v = getattr(self.last, f.name)
+                out["stats_" + f.name] = v if isinstance(v, torch.Tensor) else np.float64(v)
+        else:
+            names = ("comp_rgb", "distance", "acc", "trans", "trans_rgb_bkgd")
+            for lvl, level in zip(("coarse", "fine"), self.last):
+                for name, v in zip(names, level):
+                    out[lvl + "_" + name] = v
+        return out
 
     def close(self):
         if self.g is not None:
@@ -411,6 +463,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--trace-steps", action="store_true", help="print the host time of every step() call of every timed window to stderr (diagnostics)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: rooflines, the MFMA ceiling, stability windows, the other backward "
+                         "modes / precisions / launch form / workload variants, the frames, the collectives and the scaling curve, the CPU baseline "
+                         "and the parity against the oracle (--no-extra / --no-frame / --no-cpu-baseline / --no-curve leave parts out).  Off: set-up, "
+                         "warm-up, the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (train: parameters, Adam moments, gradient buffer, "
+                         "loss statistics; forward: every level's outputs) as DIR/<name>.npy, float32, at most 64 MB in all (rank 0's)")
     ap.add_argument("--workload", default="ship_straight")
     ap.add_argument("--fine", type=int, default=None, help="num_fine_samples (default: the workload's flat variant, 0)")
     ap.add_argument("--precision", default="f16x3", help="arithmetic of training and of every tapped path")
@@ -460,6 +520,9 @@ def main():
     ap.add_argument("--fail-rank", type=int, default=-1, help=argparse.SUPPRESS)      # fault injection for tests/test_rank_failure.py: this rank
     ap.add_argument("--fail-mode", choices=["exit", "hang"], default="exit", help=argparse.SUPPRESS)   # dies / stops responding after the warm-up
     args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline only: everything that takes runs (or checks) of its own is behind --full
+        args.extra, args.frame, args.no_cpu_baseline, args.curve = False, False, True, False
     args.backward = {"f32": "f16x3", "tf32": "f16"}.get(args.backward, args.backward)
     global TABLE_LAYOUT
     TABLE_LAYOUT = args.table_layout
@@ -556,9 +619,11 @@ def main():
     gc.collect()
     gc.freeze()
     dt = timed_steps(stepper, args.warmup, args.steps, barrier, D, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(stepper.outputs(), args.dump_outputs)      # before anything below takes another step on this stepper
     graph_used = stepper.g is not None
     replicas = None
-    if train and D.active():
+    if args.full and train and D.active():
         # data-parallel invariants after every step so far (prime + warm-up + timed): the replicas' parameters are the same BITS (every rank
         # applied the same Adam arithmetic to the same reduced gradient) although every rank drew its own rays and keys (train.py:338-339)
         iv = stepper.tstate.theta.detach().view(torch.int32).to(torch.int64)
@@ -599,7 +664,7 @@ def main():
             if rank == 0:
                 curve["n"].append(n); curve["ms_per_step"].append(1e3 * dt_n / curve["steps"]); curve["rays_per_s"].append(B * n * curve["steps"] / dt_n)
     coll = None
-    if train and D.active():
+    if args.full and train and D.active():
         # the step's one exchange, timed with events on the launch stream: the all-reduce alone (back to back, nothing else queued), and what
         # of it a step cannot hide = (step with the collective) - (step with it skipped; the replicas' parameters diverge there, timing only)
         G = stepper.tstate.grads
@@ -643,106 +708,107 @@ def main():
         graph_replay = {"launch": "one hipGraphLaunch per step" if not args.graph else "stream launches (two whole-path C calls per step)",
                         "ms_per_step": 1e3 * dt_g / 10, "rays_per_s": B * world * 10 / dt_g}
 
-    # ---- per-kernel roofline of the dominant kernels, HIP events on the launch stream ----------------------------------------------
     from samplenerfro_amd import ops, _lib
-    rnerf_cus = _lib.load().rnerf_device_cus()
     S = cfg["S"]
     N = S * cfg["P"]
-    path_pd, path_dr, _, _ = ops.march(model.table, model.spec, rays.origins, rays.viewdirs, cfg["near"], cfg["far"], N)
-    jit = model._jitter_dev(model.make_jitter(key))
     prec_fwd = model.precision if train else model.eval_precision       # the arithmetic the measured pass runs its NerfMLP in
     prec_fwd_name = args.precision if train else args.eval_precision
-    packed = model._packed_weights(variables, "coarse_mlp", prec_fwd)
-    reps = max(5, min(args.steps, 20))
+    # ---- per-kernel roofline of the dominant kernels, HIP events on the launch stream ----------------------------------------------
+    if args.full:
+        rnerf_cus = _lib.load().rnerf_device_cus()
+        path_pd, path_dr, _, _ = ops.march(model.table, model.spec, rays.origins, rays.viewdirs, cfg["near"], cfg["far"], N)
+        jit = model._jitter_dev(model.make_jitter(key))
+        packed = model._packed_weights(variables, "coarse_mlp", prec_fwd)
+        reps = max(5, min(args.steps, 20))
 
-    def timed(fn):
-        fn(); torch.cuda.synchronize()
-        e = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
-        e[0].record()
-        for i in range(reps):
-            fn(); e[i + 1].record()
-        torch.cuda.synchronize()
-        return float(np.mean([e[i].elapsed_time(e[i + 1]) for i in range(reps)]))
+        def timed(fn):
+            fn(); torch.cuda.synchronize()
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
+            e[0].record()
+            for i in range(reps):
+                fn(); e[i + 1].record()
+            torch.cuda.synchronize()
+            return float(np.mean([e[i].elapsed_time(e[i + 1]) for i in range(reps)]))
 
-    sustained = sustained_mfma_tflops(device, rnerf_cus)       # this chip, this run: the all-CU MFMA ceiling (f16 / bf16 32x32x16)
-    sus16 = sustained["f16"] if sustained else None
-    out_raw = torch.empty((S, B, 4), dtype=torch.float32, device=device)
-    mlp_ms = timed(lambda: ops.nerfmlp_forward(packed, prec_fwd, path_pd, path_dr, jit, S, B, out=out_raw))
-    mlp_flops = MLP_FLOP_PER_ROW * S * B
-    mlp_achieved = mlp_flops / (mlp_ms * 1e-3)
-    # march kernel (HBM-bound by its algorithmic gather bytes: 8 corners x 16 B per step)
-    march_ms = timed(lambda: ops.march(model.table, model.spec, rays.origins, rays.viewdirs, cfg["near"], cfg["far"], N, out=(path_pd, path_dr)))
-    march_bytes = B * (N * 128 + 24)
-    march_achieved = march_bytes / (march_ms * 1e-3)
+        sustained = sustained_mfma_tflops(device, rnerf_cus)       # this chip, this run: the all-CU MFMA ceiling (f16 / bf16 32x32x16)
+        sus16 = sustained["f16"] if sustained else None
+        out_raw = torch.empty((S, B, 4), dtype=torch.float32, device=device)
+        mlp_ms = timed(lambda: ops.nerfmlp_forward(packed, prec_fwd, path_pd, path_dr, jit, S, B, out=out_raw))
+        mlp_flops = MLP_FLOP_PER_ROW * S * B
+        mlp_achieved = mlp_flops / (mlp_ms * 1e-3)
+        # march kernel (HBM-bound by its algorithmic gather bytes: 8 corners x 16 B per step)
+        march_ms = timed(lambda: ops.march(model.table, model.spec, rays.origins, rays.viewdirs, cfg["near"], cfg["far"], N, out=(path_pd, path_dr)))
+        march_bytes = B * (N * 128 + 24)
+        march_achieved = march_bytes / (march_ms * 1e-3)
 
-    # ---- training kernels, each alone with HIP events on the launch stream
-    train_kernels = []
-    if train:
-        lib = _lib.load()
-        rows = S * B
-        BW = _lib.BACKWARDS[args.backward]
-        pbwd = ops.nerfmlp_pack_bwd(variables["flat"]["coarse_mlp"], None, BW)
-        packed = model._packed_weights(variables, "coarse_mlp")
-        raw_t, save_t = ops.nerfmlp_forward_train(packed, model.precision, path_pd, path_dr, jit, S, B, BW)
-        d_raw = torch.randn((S, B, 4), device=device) * 1e-3
-        dy_t = torch.empty(lib.rnerf_nerfmlp_dy_bytes(rows, BW), dtype=torch.uint8, device=device)
-        ws_t = torch.empty(lib.rnerf_nerfmlp_wgrad_workspace_bytes(), dtype=torch.uint8, device=device)
-        g_t = torch.empty(_lib.NERFMLP_PARAMS, device=device)
-        jp = jit.data_ptr()
-        t_f = timed(lambda: lib.rnerf_nerfmlp_forward_train(packed.data_ptr(), model.precision, path_pd.data_ptr(), path_dr.data_ptr(), jp, S, B,
-                                                            raw_t.data_ptr(), save_t.data_ptr(), BW, 0, _lib.current_stream()))
-        t_d = timed(lambda: ops.nerfmlp_backward(pbwd, packed, model.precision, save_t, d_raw, rows, dy=dy_t, stages="d", backward=BW))
-        t_w_alone = timed(lambda: ops.nerfmlp_backward(pbwd, packed, model.precision, save_t, d_raw, rows, grads=g_t, workspace=ws_t, dy=dy_t, stages="w", backward=BW))
-        t_w = t_w_alone
-        if args.pipeline and args.stage == "radiance":
-            # IN the step the wgrad hosts the next batch's march as co-resident waves (rnerf_prefetch.beside_wgrad): timed here the same way —
-            # the march forked onto the side stream right before the wgrad, the events around the wgrad on the launch stream — so that the
-            # figure is the kernel's duration as the step (and a rocprofv3 --stats of the step) sees it, not its stand-alone best case
-            side = torch.cuda.Stream()
-            cur = torch.cuda.current_stream()
+        # ---- training kernels, each alone with HIP events on the launch stream
+        train_kernels = []
+        if train:
+            lib = _lib.load()
+            rows = S * B
+            BW = _lib.BACKWARDS[args.backward]
+            pbwd = ops.nerfmlp_pack_bwd(variables["flat"]["coarse_mlp"], None, BW)
+            packed = model._packed_weights(variables, "coarse_mlp")
+            raw_t, save_t = ops.nerfmlp_forward_train(packed, model.precision, path_pd, path_dr, jit, S, B, BW)
+            d_raw = torch.randn((S, B, 4), device=device) * 1e-3
+            dy_t = torch.empty(lib.rnerf_nerfmlp_dy_bytes(rows, BW), dtype=torch.uint8, device=device)
+            ws_t = torch.empty(lib.rnerf_nerfmlp_wgrad_workspace_bytes(), dtype=torch.uint8, device=device)
+            g_t = torch.empty(_lib.NERFMLP_PARAMS, device=device)
+            jp = jit.data_ptr()
+            t_f = timed(lambda: lib.rnerf_nerfmlp_forward_train(packed.data_ptr(), model.precision, path_pd.data_ptr(), path_dr.data_ptr(), jp, S, B,
+                                                                raw_t.data_ptr(), save_t.data_ptr(), BW, 0, _lib.current_stream()))
+            t_d = timed(lambda: ops.nerfmlp_backward(pbwd, packed, model.precision, save_t, d_raw, rows, dy=dy_t, stages="d", backward=BW))
+            t_w_alone = timed(lambda: ops.nerfmlp_backward(pbwd, packed, model.precision, save_t, d_raw, rows, grads=g_t, workspace=ws_t, dy=dy_t, stages="w", backward=BW))
+            t_w = t_w_alone
+            if args.pipeline and args.stage == "radiance":
+                # IN the step the wgrad hosts the next batch's march as co-resident waves (rnerf_prefetch.beside_wgrad): timed here the same way —
+                # the march forked onto the side stream right before the wgrad, the events around the wgrad on the launch stream — so that the
+                # figure is the kernel's duration as the step (and a rocprofv3 --stats of the step) sees it, not its stand-alone best case
+                side = torch.cuda.Stream()
+                cur = torch.cuda.current_stream()
 
-            def wgrad_with_march():
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    ops.march(model.table, model.spec, rays.origins, rays.viewdirs, cfg["near"], cfg["far"], N, out=(path_pd2, path_dr2))
-                ops.nerfmlp_backward(pbwd, packed, model.precision, save_t, d_raw, rows, grads=g_t, workspace=ws_t, dy=dy_t, stages="w", backward=BW)
-                # (no join here: the events bracket the wgrad alone; the next repetition's march waits for this wgrad, as the next step's does)
+                def wgrad_with_march():
+                    side.wait_stream(cur)
+                    with torch.cuda.stream(side):
+                        ops.march(model.table, model.spec, rays.origins, rays.viewdirs, cfg["near"], cfg["far"], N, out=(path_pd2, path_dr2))
+                    ops.nerfmlp_backward(pbwd, packed, model.precision, save_t, d_raw, rows, grads=g_t, workspace=ws_t, dy=dy_t, stages="w", backward=BW)
+                    # (no join here: the events bracket the wgrad alone; the next repetition's march waits for this wgrad, as the next step's does)
 
-            path_pd2, path_dr2 = torch.empty_like(path_pd), torch.empty_like(path_dr)
-            t_w = timed(wgrad_with_march)
-            del path_pd2, path_dr2
-        R_pad = (rows + 255) // 256 * 256
-        # sum over the wgrad jobs of (X slots + dY slots) x R x 32 B (x 2: hi + lo).  f16 modes: 11 jobs (the Dense_5 / Dense_10 concat rows and
-        # the sigma head share their operand streams with the main block: 316 slot planes); bf16 body: 14 single-segment jobs (356)
-        wgrad_slots = (8 * 32 + 2 * 20 + 17 + 24 + 10 + 9) if args.backward == "bf16" else (20 + 4 * 32 + 36 + 2 * 32 + 33 + 26 + 9)
-        wgrad_bytes = wgrad_slots * R_pad * 32 * {"f16x3": 2.0, "f16x3lo8": 1.5}.get(args.backward, 1.0)
-        # the MLP phase is MFMA-bound and its algorithmic work is 2 x 593 408 FLOP per row (forward and wgrad) / 2 x 557 696
-        # (dgrad: the encodings take no gradient).  The saved-operand / dY planes the kernels stream through HBM are an implementation
-        # choice (like the path record): reported next to it as `operand_stream`, never as the algorithmic fraction.
-        for name, ms, flop, byt in (("nerfmlp_fwd_kernel<train>", t_f, MLP_FLOP_PER_ROW * rows, None),
-                                    ("nerfmlp_dgrad_kernel", t_d, 2 * 557696 * rows, None),
-                                    ("nerfmlp_wgrad_kernel" if args.backward == "bf16" else "nerfmlp_wgrad_tr_kernel", t_w, MLP_FLOP_PER_ROW * rows, wgrad_bytes)):
-            tk = {"kernel": name, "bound": "mfma", "achieved": flop / (ms * 1e-3) / 1e12, "peak": PEAK_MFMA_16BIT / 1e12,
-                  "unit": "TFLOP/s", "frac": flop / (ms * 1e-3) / PEAK_MFMA_16BIT, "avg_launch_ms": ms, "algorithmic_flop_per_launch": flop}
-            # MFMAs per algorithmic product: the forward in its precision; dgrad / wgrad: 3 with hi + lo planes, (W hi + W lo) x dY = 2 / 1 in f16, 2 / 1 in bf16
-            npass = MFMA_PASSES[args.precision] if "fwd" in name else ({"f16x3": 3, "f16x3lo8": 3, "f16": (1 if args.precision == "f16" else 2), "bf16": 2}[args.backward] if "dgrad" in name else {"f16x3": 3, "f16x3lo8": 3, "f16": 1, "bf16": 1}[args.backward])
-            with_pass_ceiling(tk, npass, sustained["bf16"] if (sustained and args.backward == "bf16" and "fwd" not in name) else sus16)
-            if byt is not None:
-                tk["avg_launch_ms_alone"] = t_w_alone
-                tk["launched"] = ("with the next batch's march co-resident, as in the step" if t_w is not t_w_alone else "alone")
-                # What bounds the wgrad is the HBM stream of its operands — X and dY of every layer, read exactly once, 4 B per value in the
-                # fp32-grade mode (f16 hi + lo: the size of the fp32 tensors the reference's backward reads) — not the matrix pipe (0.50 busy):
-                # reported as an HBM roofline, with the MFMA view of the same launch beside it
-                mf = {k: tk[k] for k in ("achieved", "peak", "unit", "frac", "algorithmic_flop_per_launch", "passes", "sustained_mfma_tflops", "frac_of_pass_ceiling") if k in tk}
-                for k in ("passes", "sustained_mfma_tflops", "frac_of_pass_ceiling"):
-                    tk.pop(k, None)
-                tk.update({"bound": "hbm", "achieved": byt / (ms * 1e-3) / 1e9, "peak": PEAK_HBM / 1e9, "unit": "GB/s", "frac": byt / (ms * 1e-3) / PEAK_HBM,
-                           "algorithmic_bytes_per_launch": byt, "mfma": mf,
-                           "bytes_note": "%d slot planes x 32 B x %d plane(s) per row: the saved activations and the gradients of every layer, read "
-                                         "once (DESIGN.md §3.3); `traffic` = the PMC counters' bytes of the same launch" % (wgrad_slots, 2 if args.backward in ("f16x3", "f16x3lo8") else 1)})
-            train_kernels.append(tk)
-        del raw_t, save_t, dy_t, ws_t
-        torch.cuda.empty_cache()
+                path_pd2, path_dr2 = torch.empty_like(path_pd), torch.empty_like(path_dr)
+                t_w = timed(wgrad_with_march)
+                del path_pd2, path_dr2
+            R_pad = (rows + 255) // 256 * 256
+            # sum over the wgrad jobs of (X slots + dY slots) x R x 32 B (x 2: hi + lo).  f16 modes: 11 jobs (the Dense_5 / Dense_10 concat rows and
+            # the sigma head share their operand streams with the main block: 316 slot planes); bf16 body: 14 single-segment jobs (356)
+            wgrad_slots = (8 * 32 + 2 * 20 + 17 + 24 + 10 + 9) if args.backward == "bf16" else (20 + 4 * 32 + 36 + 2 * 32 + 33 + 26 + 9)
+            wgrad_bytes = wgrad_slots * R_pad * 32 * {"f16x3": 2.0, "f16x3lo8": 1.5}.get(args.backward, 1.0)
+            # the MLP phase is MFMA-bound and its algorithmic work is 2 x 593 408 FLOP per row (forward and wgrad) / 2 x 557 696
+            # (dgrad: the encodings take no gradient).  The saved-operand / dY planes the kernels stream through HBM are an implementation
+            # choice (like the path record): reported next to it as `operand_stream`, never as the algorithmic fraction.
+            for name, ms, flop, byt in (("nerfmlp_fwd_kernel<train>", t_f, MLP_FLOP_PER_ROW * rows, None),
+                                        ("nerfmlp_dgrad_kernel", t_d, 2 * 557696 * rows, None),
+                                        ("nerfmlp_wgrad_kernel" if args.backward == "bf16" else "nerfmlp_wgrad_tr_kernel", t_w, MLP_FLOP_PER_ROW * rows, wgrad_bytes)):
+                tk = {"kernel": name, "bound": "mfma", "achieved": flop / (ms * 1e-3) / 1e12, "peak": PEAK_MFMA_16BIT / 1e12,
+                      "unit": "TFLOP/s", "frac": flop / (ms * 1e-3) / PEAK_MFMA_16BIT, "avg_launch_ms": ms, "algorithmic_flop_per_launch": flop}
+                # MFMAs per algorithmic product: the forward in its precision; dgrad / wgrad: 3 with hi + lo planes, (W hi + W lo) x dY = 2 / 1 in f16, 2 / 1 in bf16
+                npass = MFMA_PASSES[args.precision] if "fwd" in name else ({"f16x3": 3, "f16x3lo8": 3, "f16": (1 if args.precision == "f16" else 2), "bf16": 2}[args.backward] if "dgrad" in name else {"f16x3": 3, "f16x3lo8": 3, "f16": 1, "bf16": 1}[args.backward])
+                with_pass_ceiling(tk, npass, sustained["bf16"] if (sustained and args.backward == "bf16" and "fwd" not in name) else sus16)
+                if byt is not None:
+                    tk["avg_launch_ms_alone"] = t_w_alone
+                    tk["launched"] = ("with the next batch's march co-resident, as in the step" if t_w is not t_w_alone else "alone")
+                    # What bounds the wgrad is the HBM stream of its operands — X and dY of every layer, read exactly once, 4 B per value in the
+                    # fp32-grade mode (f16 hi + lo: the size of the fp32 tensors the reference's backward reads) — not the matrix pipe (0.50 busy):
+                    # reported as an HBM roofline, with the MFMA view of the same launch beside it
+                    mf = {k: tk[k] for k in ("achieved", "peak", "unit", "frac", "algorithmic_flop_per_launch", "passes", "sustained_mfma_tflops", "frac_of_pass_ceiling") if k in tk}
+                    for k in ("passes", "sustained_mfma_tflops", "frac_of_pass_ceiling"):
+                        tk.pop(k, None)
+                    tk.update({"bound": "hbm", "achieved": byt / (ms * 1e-3) / 1e9, "peak": PEAK_HBM / 1e9, "unit": "GB/s", "frac": byt / (ms * 1e-3) / PEAK_HBM,
+                               "algorithmic_bytes_per_launch": byt, "mfma": mf,
+                               "bytes_note": "%d slot planes x 32 B x %d plane(s) per row: the saved activations and the gradients of every layer, read "
+                                             "once (DESIGN.md §3.3); `traffic` = the PMC counters' bytes of the same launch" % (wgrad_slots, 2 if args.backward in ("f16x3", "f16x3lo8") else 1)})
+                train_kernels.append(tk)
+            del raw_t, save_t, dy_t, ws_t
+            torch.cuda.empty_cache()
 
     # ---- the arithmetic `north_star` names — ONE 16-bit MFMA per product — as labelled legs of the same workload (never the headline: 11 / 8
     #      significand bits against the reference's fp32).  They separate "cost of fp32 grade" from "engine efficiency": same engines, same
@@ -892,7 +958,7 @@ def main():
         del th_lag, th_in, g_ref
         torch.cuda.empty_cache()
 
-    traffic, sq, pmc_meta = pmc_lookup(args.workload, fine, B, args.mode, args.backward, rnerf_cus, prec_fwd_name)
+    traffic, sq, pmc_meta = pmc_lookup(args.workload, fine, B, args.mode, args.backward, rnerf_cus, prec_fwd_name) if args.full else ({}, {}, None)
 
     def traffic_of(prefix):
         for k, v in traffic.items():
@@ -1086,43 +1152,44 @@ def main():
                                         else "one whole-path C call per batch (rnerf_forward)")),
                        "pipeline": ("none" if not args.pipeline else ("march(k+1) on a side branch beside the tail of step k" if train
                                                                           else "march(k+1) on a side stream overlaps MLP(k)"))},
-            "roofline": {"kernel": "nerfmlp_fwd_kernel", "bound": "mfma", "achieved": mlp_achieved / 1e12, "peak": PEAK_MFMA_16BIT / 1e12,
-                         "unit": "TFLOP/s", "frac": mlp_achieved / PEAK_MFMA_16BIT, "traffic": traffic_of("nerfmlp_fwd_kernel<%d, 0, 0," % prec_fwd) if pmc_matches_precision else None,
-                         "avg_launch_ms": mlp_ms, "algorithmic_flop_per_launch": mlp_flops,
-                         # computed, not a counter: MFMA flops issued (3 passes in the x3 modes) / (launch time x 2.5 PF)
-                         "precision": prec_fwd_name,
-                         "mfma_issue_frac_computed": {"f16x3": 3, "bf16x3": 3, "f16x2": 2, "f16f8": 3}.get(prec_fwd_name, 1) * mlp_achieved / PEAK_MFMA_16BIT,
-                         "counters": counters_of("nerfmlp_fwd_kernel<%d, 0, 0," % prec_fwd) if pmc_matches_precision else None,
-                         "passes": MFMA_PASSES.get(prec_fwd_name, 1), "sustained_mfma_tflops": (sustained or {}).get("bf16" if prec_fwd_name.startswith("bf16") else "f16"),
-                         "frac_of_pass_ceiling": (MFMA_PASSES.get(prec_fwd_name, 1) * mlp_achieved / 1e12 / (sustained or {}).get("bf16" if prec_fwd_name.startswith("bf16") else "f16"))
-                         if sustained else None},
-            "roofline_march": {"kernel": "march_kernel", "bound": "hbm", "achieved": march_achieved / 1e9, "peak": PEAK_HBM / 1e9,
-                               "unit": "GB/s", "frac": march_achieved / PEAK_HBM, "traffic": traffic_of("march_kernel"), "avg_launch_ms": march_ms,
-                               "algorithmic_bytes_per_launch": march_bytes},
         }
-        if train:
-            # the dominant kernel of a train step: the longest of training forward / dgrad / wgrad (algorithmic FLOP against the MFMA peak)
-            fk = "nerfmlp_fwd_kernel<%d, 0, %d," % (_lib.PRECISIONS[args.precision], {"f16x3": 2, "f16x3lo8": 3}.get(args.backward, 1))      # (+ the tile-size argument)
-            for tk, pref in zip(train_kernels, (fk, "nerfmlp_dgrad_kernel", "nerfmlp_wgrad")):
-                tk["traffic"] = traffic_of(pref)
-                tk["counters"] = counters_of(pref)
-            line["roofline_forward_kernel"] = line["roofline"]
-            # plain maximum of the measured stand-alone launch times; the three are within a few % of each other, so the line also says how
-            # close the runner-up is (in the step itself the wgrad hosts the next batch's march and is the longest: profiles/r04/train_step_timeline.txt)
-            by_ms = sorted(train_kernels, key=lambda t: -t["avg_launch_ms"])
-            line["roofline"] = dict(by_ms[0])
-            line["roofline"]["tie_within_frac"] = 1.0 - by_ms[1]["avg_launch_ms"] / by_ms[0]["avg_launch_ms"]
-            line["roofline"]["runner_up"] = by_ms[1]["kernel"]
-            line["roofline_train_kernels"] = train_kernels
-            # the whole step against the MFMA peak: SURVEY §8(d)'s algorithmic FLOP (forward + dgrad + wgrad ~ 3 x forward) / ms_per_step
-            step_flop = 3.0 * flop_per_ray_fwd * B
-            line["roofline_step"] = {"bound": "mfma", "algorithmic_flop_per_step": step_flop, "achieved": step_flop / (dt / args.steps) / 1e12,
-                                     "peak": PEAK_MFMA_16BIT / 1e12, "unit": "TFLOP/s", "frac": step_flop / (dt / args.steps) / PEAK_MFMA_16BIT,
-                                     "note": "3 x (mlp_rows_per_ray x 1 186 816 + 112 896) FLOP per ray; the fp32-grade modes issue 3 MFMAs per product, "
-                                             "so MFMA issue is ~3 x this fraction (DESIGN.md §4: the 3-pass floor)"}
-        line["sustained_mfma"] = {"tflops": sustained, "what": "back-to-back v_mfma_f32_32x32x16 on every CU, no memory traffic, measured in this run "
-                                  "(csrc/ubench/mfma_rate.hip): the matrix pipe's ceiling under this chip's power limit; `frac_of_pass_ceiling` of a "
-                                  "roofline object = achieved x passes / this"}
+        if args.full:
+            line["roofline"] = {"kernel": "nerfmlp_fwd_kernel", "bound": "mfma", "achieved": mlp_achieved / 1e12, "peak": PEAK_MFMA_16BIT / 1e12,
+                                "unit": "TFLOP/s", "frac": mlp_achieved / PEAK_MFMA_16BIT, "traffic": traffic_of("nerfmlp_fwd_kernel<%d, 0, 0," % prec_fwd) if pmc_matches_precision else None,
+                                "avg_launch_ms": mlp_ms, "algorithmic_flop_per_launch": mlp_flops,
+                                # computed, not a counter: MFMA flops issued (3 passes in the x3 modes) / (launch time x 2.5 PF)
+                                "precision": prec_fwd_name,
+                                "mfma_issue_frac_computed": {"f16x3": 3, "bf16x3": 3, "f16x2": 2, "f16f8": 3}.get(prec_fwd_name, 1) * mlp_achieved / PEAK_MFMA_16BIT,
+                                "counters": counters_of("nerfmlp_fwd_kernel<%d, 0, 0," % prec_fwd) if pmc_matches_precision else None,
+                                "passes": MFMA_PASSES.get(prec_fwd_name, 1), "sustained_mfma_tflops": (sustained or {}).get("bf16" if prec_fwd_name.startswith("bf16") else "f16"),
+                                "frac_of_pass_ceiling": (MFMA_PASSES.get(prec_fwd_name, 1) * mlp_achieved / 1e12 / (sustained or {}).get("bf16" if prec_fwd_name.startswith("bf16") else "f16"))
+                                if sustained else None}
+            line["roofline_march"] = {"kernel": "march_kernel", "bound": "hbm", "achieved": march_achieved / 1e9, "peak": PEAK_HBM / 1e9,
+                                      "unit": "GB/s", "frac": march_achieved / PEAK_HBM, "traffic": traffic_of("march_kernel"), "avg_launch_ms": march_ms,
+                                      "algorithmic_bytes_per_launch": march_bytes}
+            if train:
+                # the dominant kernel of a train step: the longest of training forward / dgrad / wgrad (algorithmic FLOP against the MFMA peak)
+                fk = "nerfmlp_fwd_kernel<%d, 0, %d," % (_lib.PRECISIONS[args.precision], {"f16x3": 2, "f16x3lo8": 3}.get(args.backward, 1))      # (+ the tile-size argument)
+                for tk, pref in zip(train_kernels, (fk, "nerfmlp_dgrad_kernel", "nerfmlp_wgrad")):
+                    tk["traffic"] = traffic_of(pref)
+                    tk["counters"] = counters_of(pref)
+                line["roofline_forward_kernel"] = line["roofline"]
+                # plain maximum of the measured stand-alone launch times; the three are within a few % of each other, so the line also says how
+                # close the runner-up is (in the step itself the wgrad hosts the next batch's march and is the longest: profiles/r04/train_step_timeline.txt)
+                by_ms = sorted(train_kernels, key=lambda t: -t["avg_launch_ms"])
+                line["roofline"] = dict(by_ms[0])
+                line["roofline"]["tie_within_frac"] = 1.0 - by_ms[1]["avg_launch_ms"] / by_ms[0]["avg_launch_ms"]
+                line["roofline"]["runner_up"] = by_ms[1]["kernel"]
+                line["roofline_train_kernels"] = train_kernels
+                # the whole step against the MFMA peak: SURVEY §8(d)'s algorithmic FLOP (forward + dgrad + wgrad ~ 3 x forward) / ms_per_step
+                step_flop = 3.0 * flop_per_ray_fwd * B
+                line["roofline_step"] = {"bound": "mfma", "algorithmic_flop_per_step": step_flop, "achieved": step_flop / (dt / args.steps) / 1e12,
+                                         "peak": PEAK_MFMA_16BIT / 1e12, "unit": "TFLOP/s", "frac": step_flop / (dt / args.steps) / PEAK_MFMA_16BIT,
+                                         "note": "3 x (mlp_rows_per_ray x 1 186 816 + 112 896) FLOP per ray; the fp32-grade modes issue 3 MFMAs per product, "
+                                                 "so MFMA issue is ~3 x this fraction (DESIGN.md §4: the 3-pass floor)"}
+            line["sustained_mfma"] = {"tflops": sustained, "what": "back-to-back v_mfma_f32_32x32x16 on every CU, no memory traffic, measured in this run "
+                                      "(csrc/ubench/mfma_rate.hip): the matrix pipe's ceiling under this chip's power limit; `frac_of_pass_ceiling` of a "
+                                      "roofline object = achieved x passes / this"}
         line["collectives"] = {"backend": (dist.get_backend() if dist.is_initialized() else None), "ranks": world,
                                "per_step": ("none" if not (train and D.active()) else
                                             "all-reduce(mean) of the flat gradient + stats buffer between the backward and the update; the NerfMLP "

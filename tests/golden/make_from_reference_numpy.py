@@ -186,5 +186,25 @@ def main(path=OUT):
     return path
 
 
+def check(path=OUT):
+    """`--check`: the committed vectors are what the reference computes today — same source hash, same bits (needs the reference; the
+    suite reads the committed file only).  The hash is compared BEFORE anything of the reference file is compiled or executed."""
+    if source_sha256() is None:
+        raise SystemExit(f"{SRC} is not on this machine: nothing to check against")
+    d = np.load(path)
+    committed_sha = str(d["source_sha256"])
+    if source_sha256() != committed_sha:
+        print("rnerf/datasets.py changed: read the diff, then re-run this script")
+        return False
+    meth, _ = reference_methods(expect_sha256=committed_sha)
+    again = compute(meth, inputs())
+    y = {k[4:]: d[k] for k in d.files if k.startswith("out_")}
+    bad = sorted(set(again) ^ set(y)) + [k for k in y if k in again and not (again[k].dtype == y[k].dtype and np.array_equal(again[k], y[k]))]
+    print(f"{path}: " + ("equals what the reference computes, bit for bit" if not bad else "DIFFERS in " + ", ".join(bad[:10])))
+    return not bad
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["--check"]:
+        raise SystemExit(0 if check() else 1)
     main(sys.argv[1] if len(sys.argv) > 1 else OUT)

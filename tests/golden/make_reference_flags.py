@@ -8,6 +8,7 @@ import glob
 import hashlib
 import json
 import os
+import sys
 
 REF = os.environ.get("RNERF_REFERENCE_ROOT", "/root/reference")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "reference_flags.json")
@@ -58,5 +59,17 @@ def main():
     print(f"wrote {OUT}: {len(d['defaults'])} flags, {len(d['configs'])} configs")
 
 
+def check():
+    """`--check`: the committed table is what the reference defines today (needs the reference; the suite reads the committed file only)."""
+    now = extract()
+    if now is None:
+        raise SystemExit(f"{REF} is not on this machine: nothing to check against")
+    same = json.loads(json.dumps(now, sort_keys=True)) == json.load(open(OUT))
+    print(f"{OUT}: " + ("equals what the reference defines" if same else "DIFFERS from what the reference defines: re-run this script"))
+    return same
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["--check"]:
+        raise SystemExit(0 if check() else 1)
     main()

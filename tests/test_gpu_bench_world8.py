@@ -37,7 +37,7 @@ def _line(out):
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_eight_ranks_small(scaling):
     out, _ = _torchrun(8, ["--steps", "3", "--warmup", "1", "--workload", "example", "--rays", "512", "--no-frame", "--no-cpu-baseline", "--no-extra",
-                           "--scaling", scaling])
+                           "--scaling", scaling, "--full"])
     d = _line(out)
     per = 512 if scaling == "weak" else 64
     assert d["n_gpus"] == 8 and d["scaling"] == scaling and d["config"]["rays_per_gpu"] == per and d["value"] > 0
@@ -53,10 +53,10 @@ def test_eight_ranks_small(scaling):
 
 @pytest.mark.timeout(1500)
 def test_eight_ranks_the_drivers_command():
-    """`bench.py --gpus 8 --steps K --warmup W` with every default leg on at full size (4096 rays x 128 samples per rank on the 512^3 table, the
+    """`bench.py --gpus 8 --steps K --warmup W --full` with every leg on at full size (4096 rays x 128 samples per rank on the 512^3 table, the
     variants, both frames); only K is shortened, the rank-0 CPU baseline left out and the hierarchical ship_* variants (35 GB of saved operands per
     rank at 4096 x 512 rows — a GPU's worth, but here eight ranks share one device's 288 GB) run 1024 rays per rank."""
-    out, took = _torchrun(8, ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--variant-rays", "1024"], limit=1400)
+    out, took = _torchrun(8, ["--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--variant-rays", "1024"], limit=1400)
     d = _line(out)
     assert d["n_gpus"] == 8 and d["config"]["rays_per_gpu"] == 4096 and d["scaling"] == "weak" and d["metric"] == "rays/sec (train step)"
     assert d["collectives"]["ranks"] == 8 and d["collectives"]["replicas"]["parameters_bit_identical"] is True

@@ -1,8 +1,8 @@
 """Rows G2, G3 and 8f N4 against vectors computed BY THE REFERENCE (tests/golden/reference_numpy.npz, made by
 tests/golden/make_from_reference_numpy.py: the reference's four numpy-only methods — Dataset._generate_rays, OpenCV._generate_rays,
 Grid._linear3, Grid._compute_grad, rnerf/datasets.py:216-242,278-322,486-518 — executed from its own source).  Unlike every other golden
-file of this repository these numbers do not come from the restatement under oracle/: they pin it, and through it the HIP entry points."""
-import importlib.util
+file of this repository these numbers do not come from the restatement under oracle/: they pin it, and through it the HIP entry points.
+`python tests/golden/make_from_reference_numpy.py --check` recomputes them where the reference is present."""
 import os
 
 import numpy as np
@@ -24,22 +24,6 @@ def _load():
 
 def _grid(x):
     return [int(v) for v in x["ndim"]], [float(v) for v in x["nmin"]], [float(v) for v in x["nmax"]]
-
-
-def test_the_committed_vectors_are_what_the_reference_computes():
-    """Wherever the reference is on the machine (the build container; not the GPU box) the generator is run again: same source hash, same bits."""
-    spec = importlib.util.spec_from_file_location("make_from_reference_numpy", os.path.join(HERE, "golden", "make_from_reference_numpy.py"))
-    gen = importlib.util.module_from_spec(spec); spec.loader.exec_module(gen)
-    if gen.source_sha256() is None:
-        pytest.skip("the reference is not on this machine")
-    x, y, committed_sha = _load()
-    # the hash is compared BEFORE anything of the (untrusted) reference file is compiled or executed
-    assert gen.source_sha256() == committed_sha, "rnerf/datasets.py changed: read the diff, then re-run tests/golden/make_from_reference_numpy.py"
-    meth, sha = gen.reference_methods(expect_sha256=committed_sha)
-    again = gen.compute(meth, gen.inputs())
-    assert set(again) == set(y)
-    for k in y:
-        assert again[k].dtype == y[k].dtype and np.array_equal(again[k], y[k]), k
 
 
 def test_oracle_ray_generation_equals_the_references_bit_for_bit():
