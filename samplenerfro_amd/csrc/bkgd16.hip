@@ -17,7 +17,7 @@ namespace rnerf {
 // training forward: the same fp32 layout as bkgd_fwd_kernel (the backward kernels do not care which arithmetic produced X_k).
 // RNERF_BKGD_EXACT=1 selects the exact-fp32 kernels (they stay the arbiter of this one: tests/test_gpu_parity.py).
 // (A three-instruction split — v_cvt_pk_f16_f32, then v_fma_mixlo_f16 / v_fma_mixhi_f16 subtracting the f16 half straight from the packed
-//  word — gives the same bits alone (tools/r04/probes/mix_split_probe.hip) but NaNs in this kernel: inline asm hides the partial-register
+//  word — gives the same bits alone (profiles/r04/bkgd16.txt) but NaNs in this kernel: inline asm hides the partial-register
 //  writes from the compiler's hazard recogniser.  It bought 1 us of 21: the kernel is bound by latency, not by its conversions.)
 __device__ __forceinline__ void bkgd16_split2(float a, float b, uint32_t& hi, uint32_t& lo) { split2<true>(a, b, hi, lo); }
 __device__ __forceinline__ void bkgd16_split8(const float (&w)[8], uint4& hi, uint4& lo) {

@@ -171,14 +171,6 @@ __device__ __forceinline__ void trilinear_load(const float4* __restrict__ tab, c
     const unsigned ax0 = (unsigned)(x0 >> 1) * g.sa[0] + (unsigned)(x0 & 1) * g.sb[0], ax1 = (unsigned)(x1 >> 1) * g.sa[0] + (unsigned)(x1 & 1) * g.sb[0];
     const unsigned ay0 = (unsigned)(y0 >> 1) * g.sa[1] + (unsigned)(y0 & 1) * g.sb[1], ay1 = (unsigned)(y1 >> 1) * g.sa[1] + (unsigned)(y1 & 1) * g.sb[1];
     const unsigned az0 = (unsigned)(z0 >> 1) * g.sa[2] + (unsigned)(z0 & 1) * g.sb[2], az1 = (unsigned)(z1 >> 1) * g.sa[2] + (unsigned)(z1 & 1) * g.sb[2];
-#ifdef RNERF_TRILINEAR_NOLOAD      /* profiling ablation: the address arithmetic without the 8 gathers */
-    {
-      const float f = __uint_as_float(0x3f800000u + ((ax0 + ay0 + az0 + ax1 + ay1 + az1) & 16u) / 16u);
-      const float4 v = make_float4(f, 0.f, 0.f, 0.f);
-      c.d000 = v; c.d100 = v; c.d001 = v; c.d101 = v; c.d010 = v; c.d110 = v; c.d011 = v; c.d111 = v;
-      return;
-    }
-#endif
     const unsigned b00 = ax0 + ay0, b10 = ax1 + ay0, b01 = ax0 + ay1, b11 = ax1 + ay1;
     c.d000 = *(const float4*)(tb + (b00 + az0)); c.d100 = *(const float4*)(tb + (b10 + az0));
     c.d001 = *(const float4*)(tb + (b00 + az1)); c.d101 = *(const float4*)(tb + (b10 + az1));

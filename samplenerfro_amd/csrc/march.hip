@@ -33,10 +33,7 @@ struct MarchParams {
 // between barriers c and c + 1, the marcher overwrites that half of the ring only after barrier c + 1.  Same values, same bits.
 // With the record gone a step takes 0.26 us, and two steps of lead no longer cover an HBM round trip on a 512^3 table (2.1 GB): the
 // corners are gathered kMarchAhead steps ahead, into kMarchAhead + 1 register sets that rotate through an unrolled trip.
-#ifndef RNERF_MARCH_AHEAD
-#define RNERF_MARCH_AHEAD 2
-#endif
-constexpr int kMarchAhead = RNERF_MARCH_AHEAD;
+constexpr int kMarchAhead = 2;
 constexpr int kMarchSets = kMarchAhead + 1;
 constexpr int kMarchChunk = kMarchSets <= 4 ? 2 * kMarchSets : kMarchSets;      // nodes per ring half (a multiple of the register rotation); 2 x C x 512 B of LDS
 static_assert(2 * kMarchChunk * 512 <= 12 * 1024, "the ring must fit beside the weight-gradient kernel's LDS (148 KiB)");
@@ -55,8 +52,8 @@ __global__ void __launch_bounds__(128) march_kernel(const float* __restrict__ ta
   __shared__ float2 ring[2][C][64];               // (p, d) of the lane's coordinate, per node
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  // rays_per_wg = 16 (product), 8 or 4 (experiment, RNERF_MARCH_RPW): with fewer than 16 the upper quads of the wave replay the lower ones
-  // (same values to the same addresses, no divergence).
+  // rays_per_wg: 16 (rnerf_march), 8 or 4: with fewer than 16 the upper quads of the wave replay the lower ones (same values to the same
+  // addresses, no divergence).
   const int q = lane & 3;
   int r = blockIdx.x * rays_per_wg + ((lane >> 2) & (rays_per_wg - 1));
   if (r >= B) r = B - 1;   // surplus quads replay the last ray (same values to the same addresses, no divergence)
@@ -82,13 +79,8 @@ __global__ void __launch_bounds__(128) march_kernel(const float* __restrict__ ta
         if (k > 0) rt = fadd(rt, fsqrt(quad_sumsq3(fsub(p_prev, p))));
         p_prev = p;
         const float nrm = fsqrt(fmaxf(quad_sumsq3(d), 1e-6f));
-#ifdef RNERF_MARCH_NT
-        __builtin_nontemporal_store(q < 3 ? p : rt, out_pd);
-        __builtin_nontemporal_store(q < 3 ? fdiv(d, nrm) : 0.f, out_dr);
-#else
         *out_pd = q < 3 ? p : rt;
         *out_dr = q < 3 ? fdiv(d, nrm) : 0.f;
-#endif
         out_pd += node_stride; out_dr += node_stride;
       }
     }
@@ -129,10 +121,6 @@ __global__ void __launch_bounds__(128) march_kernel(const float* __restrict__ ta
     const unsigned y0 = quad_bcast_i<1>(m0), y1 = quad_bcast_i<1>(m1);
     const unsigned z0 = quad_bcast_i<2>(m0) + cofs, z1 = quad_bcast_i<2>(m1) + cofs;
     const unsigned b00 = quad_bcast_i<0>(m0) + y0, b10 = quad_bcast_i<0>(m1) + y0, b01 = quad_bcast_i<0>(m0) + y1, b11 = quad_bcast_i<0>(m1) + y1;
-#if defined(RNERF_MARCH_ABL) && (RNERF_MARCH_ABL & 1)   /* profiling ablation: no gathers */
-    for (int i_ = 0; i_ < 8; ++i_) o.c[i_] = __uint_as_float(0x3f800000u + ((b00 + z0 + b11 + z1) & 1u));
-    return;
-#endif
     o.c[0] = *(const float*)(tabc + (b00 + z0)); o.c[1] = *(const float*)(tabc + (b10 + z0));
     o.c[2] = *(const float*)(tabc + (b00 + z1)); o.c[3] = *(const float*)(tabc + (b10 + z1));
     o.c[4] = *(const float*)(tabc + (b01 + z0)); o.c[5] = *(const float*)(tabc + (b11 + z0));
@@ -155,18 +143,12 @@ __global__ void __launch_bounds__(128) march_kernel(const float* __restrict__ ta
   auto one_step = [&](int k, Corners& cn, Corners& nx, float2* slot) {
     *slot = make_float2(p, d);                     // the node record is the recorder's business
     // ---- VoxMLP._linear3 addressing (ior_utils.py:188-211): one coordinate per lane
-#if defined(RNERF_MARCH_ABL) && (RNERF_MARCH_ABL & 4)   /* profiling ablation: f32 multiply instead of the f64 product */
-    const float x = fmul(fsub(p, nmin_q), (float)rcp_q);
-#else
     const float x = div_const(fsub(p, nmin_q), rcp_q);
-#endif
     const float fx = floorf(x);
     const int i = (int)fx;
     const float t = fsub(x, fx);                   // (x - x0) / (x1 - x0), divisor exactly 1
     const int i0 = clamp0(i, hi_q), i1 = clamp0(i + 1, hi_q);
-#if !(defined(RNERF_MARCH_ABL) && (RNERF_MARCH_ABL & 8))   /* profiling ablation: no misprediction check */
     if (__builtin_amdgcn_ballot_w64(i0 != cn.i0 || i1 != cn.i1) != 0) gather(i0, i1, cn);     // mispredicted somewhere in the wave
-#endif
     // ---- speculative gather for step k + kMarchAhead
     const float dx = fsub(x, x_prev);
     predict(kMarchAhead == 2 ? fadd(x, fadd(dx, dx)) : fadd(x, fmul((float)kMarchAhead, dx)), nx);
@@ -185,11 +167,7 @@ __global__ void __launch_bounds__(128) march_kernel(const float* __restrict__ ta
     if (WANT_IOR && k < num_nodes) { *out_ior = c; out_ior += node_stride; }
     // ---- OneEikonalStep (eikonal_utils.py:41-45)
     const float n = quad_bcast<3>(c);
-#if defined(RNERF_MARCH_ABL) && (RNERF_MARCH_ABL & 2)   /* profiling ablation: no IEEE division on the chain */
-    const float s = fmul(step, n);
-#else
     const float s = fdiv(step, n);
-#endif
     p = fadd(p, fmul(s, d));
     d = fadd(d, fmul(step, c));
   };
@@ -226,9 +204,7 @@ extern "C" int rnerf_march(const float* table, const rnerf_grid* g, const float*
   // rays per workgroup (marcher + recorder wave): 16 = every quad of the wave.  Spreading a 4096-ray batch over twice / four times the
   // workgroups (8 / 4 rays each, two / four marching waves per CU) was measured SLOWER (round 4, profiles/r04/march_experiments.txt:
   // 0.35 -> 0.45 ms at 64^3, 0.53 -> 0.57 at 512^3): the waves of a CU share its vector-memory path, which is what a step waits on.
-  int rpw = 16;
-  if (const char* e = RNERF_ENV("RNERF_MARCH_RPW")) rpw = atoi(e);       // experiment switch (tools/r04/march_rpw.sh)
-  RNERF_CHECK_ARG(rpw == 16 || rpw == 8 || rpw == 4, "rnerf_march: RNERF_MARCH_RPW must be 16, 8 or 4");
+  const int rpw = 16;
   const dim3 block(128), grid((B + rpw - 1) / rpw);
   hipStream_t st = (hipStream_t)stream;
 #define LAUNCH2(I, V, K)                                                                                           \

@@ -246,11 +246,7 @@ __device__ __forceinline__ void glds16(const char* gsrc, unsigned lds_off) {
 // the same with the non-temporal policy: operand streams that are read exactly once (wgrad)
 __device__ __forceinline__ void glds16_nt(const char* gsrc, unsigned lds_off) {
   unsigned keep;
-#ifdef RNERF_WGTR_NO_NT
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-#else
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-#endif
                : "=&s"(keep) : "v"(gsrc), "s"(lds_off) : "memory");
 }
 // the same with a wave-uniform 64-bit base (SGPR pair) + a 32-bit per-lane byte offset: the address arithmetic of a stream that advances
@@ -306,7 +302,7 @@ typedef KOpsT<false> KOps;
 // ReLU as an INTEGER max on the bit pattern: max_i32(bits(x), 0) is x for x >= +0, +0 for every negative x (and -0), and — unlike
 // v_max_f32, which returns the non-NaN operand — it keeps +inf and NaN.  That matters because the activations travel as f16 parts: a hidden
 // activation above 65504 becomes hi = inf, lo = x - inf = -inf, the next layer's sums inf - inf = NaN, and with fmaxf(NaN, 0) = 0 every unit
-// of that layer silently read 0 — finite, plausible, wrong outputs (found in round 4; tools/r04/dbg_hot.py).  With the integer max the NaN
+// of that layer silently read 0 — finite, plausible, wrong outputs (found in round 4; DESIGN.md section 3.2, "Range").  With the integer max the NaN
 // reaches the outputs: out of range means non-finite, never plausible.  NO_FLOOR (= INT_MIN) turns the max into the identity (bottleneck).
 constexpr int RELU_FLOOR = 0, NO_FLOOR = (int)0x80000000u;
 __device__ __forceinline__ float relu_keep(float x, int floor_bits) {
@@ -315,10 +311,6 @@ __device__ __forceinline__ float relu_keep(float x, int floor_bits) {
 }
 
 // streaming accesses of the training tensors (written once, read once by a later kernel): keep them out of the L2 working set
-#ifdef RNERF_NO_NT
-__device__ __forceinline__ void stream_store(uint4* p, const uint4 v) { *p = v; }
-__device__ __forceinline__ uint4 stream_load(const uint4* p) { return *p; }
-#else
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void stream_store(uint4* p, const uint4 v) {
   u32x4_t t = {v.x, v.y, v.z, v.w};
@@ -328,15 +320,10 @@ __device__ __forceinline__ uint4 stream_load(const uint4* p) {
   const u32x4_t t = __builtin_nontemporal_load((const u32x4_t*)p);
   return make_uint4(t.x, t.y, t.z, t.w);
 }
-#endif
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void stream_store8(uint2* p, const uint2 v) {
-#ifdef RNERF_NO_NT
-  *p = v;
-#else
   u32x2_t t = {v.x, v.y};
   __builtin_nontemporal_store(t, (u32x2_t*)p);
-#endif
 }
 
 template <int PREC>
@@ -419,9 +406,7 @@ struct PrevConv {
       if constexpr (PP::F8X) lo[mt][2 + (p >> 1)] = f8_pair<(p & 1) != 0, true>(lo[mt][2 + (p >> 1)], x0, x1);   // fp8(x_lo 2^10)
       else if constexpr (PP::NP == 2) lo[mt][p] = pack2<PP::F16>(x0, x1);
       else lo[mt][p] = 0;
-#ifndef RNERF_FWD_NOMASK
       if constexpr (MASK) nz[mt] |= pk_min1(hi[mt][p]) << p;   // post-ReLU values are non-negative: min(u16, 1) = non-zero flag of each half
-#endif
     }
   }
   __device__ __forceinline__ KOpsT<ONE> result() const {
@@ -611,16 +596,9 @@ __device__ __forceinline__ void tile_mfma(f32x16& a0, f32x16& a1, const uint4 ah
 // one k-step (block KOFF of the slab) of MFMAs for NT n-tiles x 2 m-tiles; FIRST: accumulators start from 0.
 // The A fragments of tile t+1 are read from LDS before the MFMAs of tile t are issued.
 struct NoDma { __device__ __forceinline__ void operator()() const {} };
-// Training kernels: the four operand / gradient stores of a k-step (hi and lo parts of both m-tiles) used to be issued at the head of the
-// k-step, right behind the slab barrier and in front of the first MFMA — four 1 KiB vector stores with the matrix pipe idle (the ISA of every
-// steady k-step begins `S S S S ds_read x 10 s_waitcnt M ...`).  RNERF_SPREAD_STORES: one store behind each of tiles 2..5 instead (the store
-// hook `st` of kstep_mfma), in the MFMAs' shadow like the conversion chunks.  Measured (round 6, tools/r06/ab_wgrad.py, one box, alternating):
-// training forward 2.016 / 1.974 -> 1.963 / 1.972 ms (inside the noise), dgrad 1.771 / 1.783 -> 1.838 / 1.842 ms (its spills grow from 259 to
-// 301 registers) — the seventh re-placement of work in these engines that does not pay: OFF.
-#ifndef RNERF_SPREAD_STORES
-#define RNERF_SPREAD_STORES 0
-#endif
-struct NoStore { template <int K> __device__ __forceinline__ void part() const {} };
+// The training kernels' four operand / gradient stores of a k-step stay at its head, in front of the first MFMA.  Spread behind tiles
+// 2..5 instead (in the MFMAs' shadow, like the conversion chunks) they measured no faster in the training forward and slower in the dgrad
+// (1.771 / 1.783 -> 1.838 / 1.842 ms, its spills grow from 259 to 301 registers; DESIGN.md section 3.3, profiles/r06/README.md).
 
 // `dma` is invoked after tile 1: the weight DMA of the next slab is issued while MFMAs are already in the matrix pipe and
 // the A fragments of tiles 0..3 are already on their way (an LDS-DMA instruction costs ~100 issue cycles).
@@ -628,8 +606,8 @@ struct NoStore { template <int K> __device__ __forceinline__ void part() const {
 // number of reads in flight (latency x concurrency), not by the 256 B/clk peak.
 constexpr int FRAG_DEPTH = 4;
 
-template <int PREC, int NT, int KOFF, bool FIRST, typename W, bool NOREAD = false, typename D = NoDma, int PASSES = Prec<PREC>::PASSES, typename BOPS = KOps, typename ST = NoStore>
-__device__ __forceinline__ void kstep_mfma(f32x16 (&acc0)[8], f32x16 (&acc1)[8], const BOPS& b, const char* slab, int lane, W& work, D dma = D(), const ST& st = ST()) {
+template <int PREC, int NT, int KOFF, bool FIRST, typename W, typename D = NoDma, int PASSES = Prec<PREC>::PASSES, typename BOPS = KOps>
+__device__ __forceinline__ void kstep_mfma(f32x16 (&acc0)[8], f32x16 (&acc1)[8], const BOPS& b, const char* slab, int lane, W& work, D dma = D()) {
   using PP = Prec<PREC>;
   const uint4* a = (const uint4*)slab + lane + (size_t)KOFF * NT * PP::NP * 64;
   uint4 fh[FRAG_DEPTH], fl[FRAG_DEPTH];
@@ -651,10 +629,9 @@ __device__ __forceinline__ void kstep_mfma(f32x16 (&acc0)[8], f32x16 (&acc1)[8],
   }
 #define RNERF_TILE(T)                                                                                     \
   if constexpr (T < NT) {                                                                                 \
-    uint4 ah = fh[T % FRAG_DEPTH], al = fl[T % FRAG_DEPTH];                                               \
-    if constexpr (NOREAD) { asm volatile("" : "+v"(ah.x), "+v"(al.x)); }  /* ablation: opaque, so tiles are not CSE'd */ \
+    const uint4 ah = fh[T % FRAG_DEPTH], al = fl[T % FRAG_DEPTH];                                         \
     tile_mfma<PREC, FIRST, (T & 7), W, PASSES, BOPS>(acc0[T], acc1[T], ah, al, b, work);                  \
-    if constexpr (T + FRAG_DEPTH < NT && !NOREAD) {                                                       \
+    if constexpr (T + FRAG_DEPTH < NT) {                                                                  \
       fh[T % FRAG_DEPTH] = a[((T + FRAG_DEPTH) * PP::NP) * 64];                                           \
       fl[T % FRAG_DEPTH] = load_lo(T + FRAG_DEPTH);                                                       \
     }                                                                                                     \
@@ -662,13 +639,13 @@ __device__ __forceinline__ void kstep_mfma(f32x16 (&acc0)[8], f32x16 (&acc1)[8],
   RNERF_TILE(0) RNERF_TILE(1)
   dma();
   RNERF_TILE(2)
-  if constexpr (NT == 8) { st.template part<0>(); RNERF_PIN(); }
+  if constexpr (NT == 8) RNERF_PIN();      // scheduling boundaries behind tiles 2..5: the measured schedules of the 8-tile k-steps depend on them
   RNERF_TILE(3)
-  if constexpr (NT == 8) { st.template part<1>(); RNERF_PIN(); }
+  if constexpr (NT == 8) RNERF_PIN();
   RNERF_TILE(4)
-  if constexpr (NT == 8) { st.template part<2>(); RNERF_PIN(); }
+  if constexpr (NT == 8) RNERF_PIN();
   RNERF_TILE(5)
-  if constexpr (NT == 8) { st.template part<3>(); RNERF_PIN(); }
+  if constexpr (NT == 8) RNERF_PIN();
   RNERF_TILE(6) RNERF_TILE(7)
 #undef RNERF_TILE
 }
@@ -702,35 +679,9 @@ __device__ __forceinline__ uint32_t nz_nibbles(const uint4& o) {
 }
 __device__ __forceinline__ uint32_t nz_byte(uint32_t nib) { return (nib & 0xFu) | (nib >> 12); }   // even flags | odd flags << 4
 
-// The saves of one k-step one at a time (kstep_mfma's store hook, RNERF_SPREAD_STORES): part 0 / 1 = the hi parts of m-tile 0 / 1, 2 / 3 = the
-// lo parts (TRAIN = 2: f16, 3: e4m3 bytes).  (Namespace scope: a local class cannot have a member template.)
-template <int TRAIN, bool ONE>
-struct SaveParts {
-  uint4* save; long long save_rows, t32_0; int q, m, h; const KOpsT<ONE>& o;
-  template <int K> __device__ __forceinline__ void part() const {
-    if constexpr (TRAIN != 0) {
-#ifndef RNERF_FWD_NOSAVE
-      uint4* dst = save + sv_addr(q, t32_0, m, h);
-      if constexpr (K == 0) stream_store(dst, o.h0);
-      if constexpr (K == 1 && !ONE) stream_store(dst + (size_t)SAVE_SLOTS * 64, o.h1);
-      if constexpr (TRAIN == 2) {
-        uint4* dl = dst + sv_lo0(save_rows);
-        if constexpr (K == 2) stream_store(dl, o.l0);
-        if constexpr (K == 3 && !ONE) stream_store(dl + (size_t)SAVE_SLOTS * 64, o.l1);
-      }
-      if constexpr (TRAIN == 3) {
-        uint2* dl = (uint2*)(save + sv_lo0(save_rows)) + sv_addr(q, t32_0, m, h);
-        if constexpr (K == 2) stream_store8(dl, lo8_pack<false>(o.l0, LO8_SCALE_X));
-        if constexpr (K == 3 && !ONE) stream_store8(dl + (size_t)SAVE_SLOTS * 64, lo8_pack<false>(o.l1, LO8_SCALE_X));
-      }
-#endif
-    }
-  }
-};
-
 // TRAIN: 0 = evaluation, 1 = training forward keeping the hi 16-bit operand parts, 2 = hi and lo parts (fp32-grade backward),
 // 3 = hi parts + the lo parts as e4m3 bytes (RNERF_BWD_F16X3_LO8: lo8 plane = uint2[...] at the lo plane's place, same (tile, slot, row, half) order)
-template <int PREC, int dbg, int TRAIN, bool ONE = false>
+template <int PREC, int MODE, int TRAIN, bool ONE = false>
 __global__ void __launch_bounds__(256, 1)
 nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ rows_pd, const float4* __restrict__ rows_dr,
                    const int* __restrict__ node_of_sample, int B, long long total_rows, int n_tiles, float4* __restrict__ out_raw,
@@ -742,10 +693,6 @@ nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ r
   // tileq != nullptr (training forward on a capped grid): tiles beyond the first round are handed out by an atomic counter (tileq[0],
   // zeroed by the launcher; tileq[1 + workgroup] passes the draw from thread 0 to the other waves) — with fewer workgroups than CUs the
   // static stride would leave most of the chip idle in a last partial round (2048 tiles over 248 workgroups: 9 rounds instead of 8.26).
-  // dbg != 0: profiling ablations, only instantiated with -DRNERF_MLP_ABLATE (results are garbage):
-  //   bit0 = skip the weight-stream loads, bit1 = skip ds_read + MFMA, bit2 = skip the barrier.
-  // Compile-time on purpose: a runtime branch per k-step would split the scheduling region and stop the compiler from
-  // interleaving the operand conversion (VALU) with the MFMAs.
   // ONE: 128-row tiles — every wave runs ONE 32-row m-tile (rows 128 tile + 32 wave + m): half the serial work per tile, for launches whose
   // 256-row tiles would leave more than half of the CUs idle.  n_tiles then counts 128-row tiles; the save layout (32-row tiles) is the same.
   using PP = Prec<PREC>;
@@ -763,19 +710,15 @@ nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ r
   constexpr float INV_SCALE = 1.0f / PP::WSCALE;
   int buf = 0;
   size_t off = 0;   // stream offset of the next slab to prefetch
-  float prof_dma = 0.f, prof_bar = 0.f, prof_tot = 0.f, prof_n = 0.f;
-  unsigned long long prof_last = __builtin_amdgcn_s_memtime();
-  // dbg & 256: shader clocks per phase of a tile (PH(k) books the time since the previous mark on phase k):
-  //   0 row loads  1 layer 0 (encoding slabs)  2 first k-step of a hidden layer (incl. its operand conversion)  3 k-steps 1..15
-  //   4 layer end (state to registers / LDS)  5 skip-concat slabs  6 sigma head  7 view layer  8 rgb head + store
-  float prof_ph[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#define PH(K) do { if constexpr ((dbg & 256) != 0) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); prof_ph[K] += (float)(t_ - prof_last); prof_last = t_; } } while (0)
+  // One shader-clock read, result unused: every measured build of this kernel has it here, so it stays until a timing A/B retires it.
+  (void)__builtin_amdgcn_s_memtime();
 
-  // dbg & 512 — REDO, the range-safe second pass (rnerf_nerfmlp_forward queues it behind every f16-based evaluation launch, in bf16x3: fp32's
+  // MODE 512 — REDO, the range-safe second pass (rnerf_nerfmlp_forward queues it behind every f16-based evaluation launch, in bf16x3: fp32's
   // exponent range): it walks the same tiles but works only on those that hold a row the first pass returned as NaN (an activation above
   // f16's 65504 or a weight >= 256, see `watch` / AUX_FLAG below) and rewrites only those rows.  The flags ARE the first pass's outputs: no
   // scratch, nothing to clear, and a launch without such a row costs one read of out_raw (8 tiles' rows in flight per barrier).
-  constexpr bool REDO = (dbg & 512) != 0;
+  // (MODE is a template parameter, not a bool, because it is part of the kernels' names.)
+  constexpr bool REDO = (MODE & 512) != 0;
   // bit k of `todo`: this workgroup's k-th tile (blockIdx.x + k gridDim.x) holds a NaN row.  Found in the prologue, while the LDS is still
   // free (four 8-byte words for the cross-wave OR; the kernel owns all 160 KiB later).  A workgroup with more than 64 tiles works on every
   // tile beyond the 64th (correct — only NaN rows are rewritten — just not skipped: > 4 M rows per launch on this chip).
@@ -808,7 +751,7 @@ nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ r
     }
   };
   const int first_tile = find_next((int)blockIdx.x);
-  if (first_tile < n_tiles) { if (!(dbg & 1)) issue_slab<SLAB>(packed, 0u, wave, lane); off = SLAB; }
+  if (first_tile < n_tiles) { issue_slab<SLAB>(packed, 0u, wave, lane); off = SLAB; }
   slab_wait_dma();
   __syncthreads();
 
@@ -837,13 +780,11 @@ nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ r
     }
 
     f32x16 acc0[8], acc1[8], prev0[8];
-    PH(0);
 
     // training forward: keep the hi parts of the operands of slot q (see SAVE_* above); padded rows are written too
     const long long t32_0 = (long long)tile * (TROWS / 32) + wave * (WROWS / 32);      // 32-row tile of m-tile 0 (m-tile 1: + 1)
     auto save_ops = [&](int q, const KOps& o) {
       if constexpr (TRAIN != 0) {
-#ifndef RNERF_FWD_NOSAVE      /* profiling ablation */
         uint4* dst = save + sv_addr(q, t32_0, m, h);
         stream_store(dst, o.h0);
         if constexpr (!ONE) stream_store(dst + (size_t)SAVE_SLOTS * 64, o.h1);          // m-tile 1 = the next 32-row tile
@@ -857,30 +798,22 @@ nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ r
           stream_store8(dl, lo8_pack<false>(o.l0, LO8_SCALE_X));
           if constexpr (!ONE) stream_store8(dl + (size_t)SAVE_SLOTS * 64, lo8_pack<false>(o.l1, LO8_SCALE_X));
         }
-#endif
       }
     };
 
-    // Range watch of the f16 operand parts (RNERF_FWD_NORANGE: ablation).  A hidden activation above f16's 65504 becomes hi = inf; the next
+    // Range watch of the f16 operand parts.  A hidden activation above f16's 65504 becomes hi = inf; the next
     // layer's sums are inf - inf = NaN (sign bit set on this hardware), which the ReLU turns into 0 — every unit of that layer would read 0
-    // and the outputs would be finite, plausible and wrong (found in round 4, tools/r04/dbg_hot.py).  So the largest |hi| bit pattern per lane
+    // and the outputs would be finite, plausible and wrong (found in round 4; DESIGN.md section 3.2, "Range").  So the largest |hi| bit pattern per lane
     // is kept (one v_pk_max_u16 per operand dword: positive f16 order like their bits, inf = 0x7C00) and a row that met inf / NaN returns NaN.
     uint32_t ovf0 = 0, ovf1 = 0;
-    auto watch = [&](const KOps& o, bool is_signed) {
-#ifndef RNERF_FWD_NORANGE
-      {                                                                 // (bf16 modes too — round 5: a non-finite position used to come out FINITE there)
-        const uint32_t am = is_signed ? 0x7FFF7FFFu : 0xFFFFFFFFu;      // the bottleneck has no ReLU: drop the sign bits
-        ovf0 = pk_maxu(pk_maxu(ovf0, o.h0.x & am), pk_maxu(pk_maxu(o.h0.y & am, o.h0.z & am), o.h0.w & am));
-        if constexpr (!ONE) ovf1 = pk_maxu(pk_maxu(ovf1, o.h1.x & am), pk_maxu(pk_maxu(o.h1.y & am, o.h1.z & am), o.h1.w & am));
-      }
-#endif
+    auto watch = [&](const KOps& o, bool is_signed) {      // (bf16 modes too — round 5: a non-finite position used to come out FINITE there)
+      const uint32_t am = is_signed ? 0x7FFF7FFFu : 0xFFFFFFFFu;      // the bottleneck has no ReLU: drop the sign bits
+      ovf0 = pk_maxu(pk_maxu(ovf0, o.h0.x & am), pk_maxu(pk_maxu(o.h0.y & am, o.h0.z & am), o.h0.w & am));
+      if constexpr (!ONE) ovf1 = pk_maxu(pk_maxu(ovf1, o.h1.x & am), pk_maxu(pk_maxu(o.h1.y & am, o.h1.z & am), o.h1.w & am));
     };
 
     uint32_t mw0 = 0, mw1 = 0;                                                // mask bytes of up to 4 k-steps, then one dword store
     auto save_mask = [&](int set, int s, uint32_t nib0, uint32_t nib1) {      // nib: nz_nibbles() of the hi operands of k-step s
-#ifdef RNERF_FWD_NOMASK       /* profiling ablation */
-      return;
-#endif
       if constexpr (TRAIN != 0) {
         if ((s & 3) == 0) { mw0 = nz_byte(nib0); mw1 = nz_byte(nib1); }
         else { mw0 |= nz_byte(nib0) << (8 * (s & 3)); mw1 |= nz_byte(nib1) << (8 * (s & 3)); }
@@ -951,21 +884,8 @@ nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ r
     NoWork nowork;
 
 #define SLAB_PREFETCH(DO_NEXT)                                                                                       \
-  do { if (DO_NEXT) { if (!(dbg & 1)) issue_slab<SLAB>(packed + off, (unsigned)((buf ^ 1) * SLAB), wave, lane); off += SLAB; } } while (0)
-#define SLAB_DONE()                                                                                                  \
-  do {                                                                                                               \
-    if constexpr ((dbg & 64) != 0) {   /* profiling: where does a slab's time go (shader clocks, summed per wave) */   \
-      const unsigned long long ta = __builtin_amdgcn_s_memtime();                                                    \
-      slab_wait_dma();                                                                                               \
-      const unsigned long long tb = __builtin_amdgcn_s_memtime();                                                    \
-      __syncthreads();                                                                                               \
-      const unsigned long long tc2 = __builtin_amdgcn_s_memtime();                                                   \
-      prof_dma += (float)(tb - ta); prof_bar += (float)(tc2 - tb); prof_tot += (float)(tc2 - prof_last); prof_last = tc2; prof_n += 1.f; \
-    } else {                                                                                                         \
-      slab_wait_dma(); if (!(dbg & 4)) __syncthreads();                                                              \
-    }                                                                                                                \
-    buf ^= 1;                                                                                                        \
-  } while (0)
+  do { if (DO_NEXT) { issue_slab<SLAB>(packed + off, (unsigned)((buf ^ 1) * SLAB), wave, lane); off += SLAB; } } while (0)
+#define SLAB_DONE() do { slab_wait_dma(); __syncthreads(); buf ^= 1; } while (0)
 
     float sig0 = 0.f, sig1 = 0.f;
 
@@ -985,18 +905,16 @@ nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ r
         SLAB_PREFETCH(true);   /* glds first: it is a scheduling boundary, conversion + MFMAs must share the region after it */ \
         if constexpr (S < 3) {                                                                                       \
           EncWork<PREC, S + 1, 30, ONE> ew(pd, h);                                                                        \
-          if (!(dbg & 2)) kstep_mfma<PREC, 8, 0, FIRST_>(acc0, acc1, cur, smem + buf * SLAB, lane, ew);              \
+          kstep_mfma<PREC, 8, 0, FIRST_>(acc0, acc1, cur, smem + buf * SLAB, lane, ew);                              \
           cur = ew.result();                                                                                         \
         } else {                                                                                                     \
-          if (!(dbg & 2)) kstep_mfma<PREC, 8, 0, false>(acc0, acc1, cur, smem + buf * SLAB, lane, seam);             \
+          kstep_mfma<PREC, 8, 0, false>(acc0, acc1, cur, smem + buf * SLAB, lane, seam);                             \
         }                                                                                                            \
         SLAB_DONE();                                                                                                 \
       }
       RNERF_PE_KSTEP(0, true, true) RNERF_PE_KSTEP(1, false, true) RNERF_PE_KSTEP(2, false, true) RNERF_PE_KSTEP(3, false, true)
-      PH(1);
       seam.finish();
       cur = seam.cv.result();
-      PH(4);
     }
 
     // bias / sigma weights of the conversion that runs in the shadow of the next hidden k-step (fetched one slab ahead, across layers too)
@@ -1018,8 +936,7 @@ nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ r
       const float* __restrict__ wsel = auxt + (l == 8 ? AUX_WSIG : AUX_ZERO);
 #define RNERF_KSTEP(S)                                                                                              \
       {                                                                                                              \
-        const SaveParts<TRAIN, ONE> sp{save, save_rows, t32_0, SAVE_L1 + 16 * (l - 1) + S, m, h, cur};                            \
-        if constexpr (!(RNERF_SPREAD_STORES && TRAIN != 0)) save_ops(SAVE_L1 + 16 * (l - 1) + S, cur);               \
+        save_ops(SAVE_L1 + 16 * (l - 1) + S, cur);                                                                   \
         watch(cur, false);                                                                                           \
         if constexpr (TRAIN != 0 && S == 0) save_mask(l - 1, 0, nz_nibbles(cur.h0), nz_nibbles(cur.h1));                  \
         if constexpr (S == 13) { load_bias8(0, bias + 256, seam.cv.b); load_bias8(0, wseam, seam.cv.ws); }           \
@@ -1032,36 +949,30 @@ nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ r
           cv.floor_v = RELU_FLOOR;                                                                                        \
           _Pragma("unroll") for (int j = 0; j < 8; ++j) { cv.b[j] = bnext[j]; cv.ws[j] = wnext[j]; }                 \
           load_state8(S + 1, cv.v1);                                                                                 \
-          if (dbg & 8) { kstep_mfma<PREC, 8, 0, S == 0, NoWork, (dbg & 16) != 0>(acc0, acc1, cur, smem + buf * SLAB, lane, nowork, dma); } \
-          else { if (!(dbg & 2)) { if constexpr (RNERF_SPREAD_STORES && TRAIN != 0) kstep_mfma<PREC, 8, 0, S == 0, PrevConv<PREC, S + 1, TRAIN != 0, true, ONE>, (dbg & 16) != 0, decltype(dma), Prec<PREC>::PASSES, KOps, SaveParts<TRAIN, ONE>>(acc0, acc1, cur, smem + buf * SLAB, lane, cv, dma, sp); else \
-            kstep_mfma<PREC, 8, 0, S == 0, PrevConv<PREC, S + 1, TRAIN != 0, true, ONE>, (dbg & 16) != 0, decltype(dma)>(acc0, acc1, cur, smem + buf * SLAB, lane, cv, dma); }              \
+          kstep_mfma<PREC, 8, 0, S == 0, PrevConv<PREC, S + 1, TRAIN != 0, true, ONE>, decltype(dma)>(acc0, acc1, cur, smem + buf * SLAB, lane, cv, dma); \
           cur = cv.result();                                                                                         \
           sig0 += cv.sg0; sig1 += cv.sg1;                                                                            \
-          save_mask(l - 1, S + 1, cv.nz[0], cv.nz[1]); }                                                             \
+          save_mask(l - 1, S + 1, cv.nz[0], cv.nz[1]);                                                               \
         } else {                                                                                                     \
           /* also for l == 5, whose last k-step is the 4th skip slab: that one runs the seam again on the final sums (no branch here: */ \
           /* a run-time choice of the work functor splits the accumulators' live ranges and hipcc spills them around it) */ \
-          if (!(dbg & 2)) { if constexpr (RNERF_SPREAD_STORES && TRAIN != 0) kstep_mfma<PREC, 8, 0, false, SeamWork<PREC, TRAIN != 0, ONE>, false, decltype(dma), Prec<PREC>::PASSES, KOps, SaveParts<TRAIN, ONE>>(acc0, acc1, cur, smem + buf * SLAB, lane, seam, dma, sp); else \
-            kstep_mfma<PREC, 8, 0, false, SeamWork<PREC, TRAIN != 0, ONE>, false, decltype(dma)>(acc0, acc1, cur, smem + buf * SLAB, lane, seam, dma); } \
+          kstep_mfma<PREC, 8, 0, false, SeamWork<PREC, TRAIN != 0, ONE>, decltype(dma)>(acc0, acc1, cur, smem + buf * SLAB, lane, seam, dma); \
         }                                                                                                            \
         if constexpr (S + 2 <= 16) { _Pragma("unroll") for (int j = 0; j < 8; ++j) { bnext[j] = bnn[j]; wnext[j] = wnn[j]; } } \
         SLAB_DONE();                                                                                                 \
       }
-      RNERF_KSTEP(0) PH(2); RNERF_KSTEP(1) RNERF_KSTEP(2) RNERF_KSTEP(3) RNERF_KSTEP(4) RNERF_KSTEP(5) RNERF_KSTEP(6) RNERF_KSTEP(7)
+      RNERF_KSTEP(0) RNERF_KSTEP(1) RNERF_KSTEP(2) RNERF_KSTEP(3) RNERF_KSTEP(4) RNERF_KSTEP(5) RNERF_KSTEP(6) RNERF_KSTEP(7)
       RNERF_KSTEP(8) RNERF_KSTEP(9) RNERF_KSTEP(10) RNERF_KSTEP(11) RNERF_KSTEP(12) RNERF_KSTEP(13) RNERF_KSTEP(14) RNERF_KSTEP(15)
 #undef RNERF_KSTEP
-      PH(3);
       if (l == 5) {   // skip concat: [x, inputs] (rnerf/model_utils.py:68-69)
         // the encoding is recomputed here on purpose (in the MFMA shadow); with the position opaque the compiler cannot keep layer 0's
         // encoded values alive across five layers instead (f16f8: it kept all 64, through scratch — 8 k clocks per skip slab instead of 4)
         asm volatile("" : "+v"(pd[0].x), "+v"(pd[0].y), "+v"(pd[0].z), "+v"(pd[1].x), "+v"(pd[1].y), "+v"(pd[1].z));
         cur = enc_ops(pd, 0, 30);
         RNERF_PE_KSTEP(0, false, false) RNERF_PE_KSTEP(1, false, false) RNERF_PE_KSTEP(2, false, false) RNERF_PE_KSTEP(3, false, false)
-        PH(5);
       }
       seam.finish();
       cur = seam.cv.result();
-      PH(4);
       sig0 += seam.cv.sg0; sig1 += seam.cv.sg1;
     }
 
@@ -1090,18 +1001,14 @@ nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ r
           load_state8(2 * SL + 3, cvB.v1);                                                                           \
           PairOfPairs<decltype(cvA)> wA(cvA);                                                                        \
           PairOfPairs<decltype(cvB)> wB(cvB);                                                                        \
-          if (!(dbg & 2)) {                                                                                          \
-            kstep_mfma<PREC, 4, 0, SL == 0>(acc0, acc1, c0, smem + buf * SLAB, lane, wA);                            \
-            kstep_mfma<PREC, 4, 1, false>(acc0, acc1, c1, smem + buf * SLAB, lane, wB);                              \
-          }                                                                                                          \
+          kstep_mfma<PREC, 4, 0, SL == 0>(acc0, acc1, c0, smem + buf * SLAB, lane, wA);                              \
+          kstep_mfma<PREC, 4, 1, false>(acc0, acc1, c1, smem + buf * SLAB, lane, wB);                                \
           c0 = cvA.result(); c1 = cvB.result();                                                                      \
           if constexpr (SL + 2 < 8) { _Pragma("unroll") for (int j = 0; j < 8; ++j) { bA[j] = bA2[j]; bB[j] = bB2[j]; } } \
         } else {                                                                                                     \
           const KOps n0 = enc_ops(dr, 0, 12), n1 = enc_ops(dr, 1, 12);                                               \
-          if (!(dbg & 2)) {                                                                                          \
-            kstep_mfma<PREC, 4, 0, false>(acc0, acc1, c0, smem + buf * SLAB, lane, nowork);                          \
-            kstep_mfma<PREC, 4, 1, false>(acc0, acc1, c1, smem + buf * SLAB, lane, nowork);                          \
-          }                                                                                                          \
+          kstep_mfma<PREC, 4, 0, false>(acc0, acc1, c0, smem + buf * SLAB, lane, nowork);                            \
+          kstep_mfma<PREC, 4, 1, false>(acc0, acc1, c1, smem + buf * SLAB, lane, nowork);                            \
           c0 = n0; c1 = n1;                                                                                          \
         }                                                                                                            \
         SLAB_DONE();                                                                                                 \
@@ -1117,9 +1024,9 @@ nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ r
       const bool has_next_tile = next_tile < n_tiles;
       if (has_next_tile) off = 0;
       SLAB_PREFETCH(has_next_tile);
-      if (!(dbg & 2)) { kstep_mfma<PREC, 4, 0, false>(acc0, acc1, c0, smem + buf * SLAB, lane, nowork); kstep_mfma<PREC, 4, 1, false>(acc0, acc1, c1, smem + buf * SLAB, lane, nowork); }
+      kstep_mfma<PREC, 4, 0, false>(acc0, acc1, c0, smem + buf * SLAB, lane, nowork);
+      kstep_mfma<PREC, 4, 1, false>(acc0, acc1, c1, smem + buf * SLAB, lane, nowork);
       SLAB_DONE();
-      PH(7);
     }
 
     // ---- heads: sigma (Dense_8, accumulated above) and rgb (Dense_11) on the fp32 view-layer output
@@ -1189,7 +1096,6 @@ nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ r
       }
       sig0 = sig0 + __shfl_xor(sig0, 32) + bsig;
       sig1 = sig1 + __shfl_xor(sig1, 32) + bsig;
-#ifndef RNERF_FWD_NORANGE
       {      // an activation outside the operand type's range somewhere along this row's chain (either half of its features); bf16: inf / NaN only
         ovf0 = pk_maxu(ovf0, (uint32_t)__shfl_xor((int)ovf0, 32));
         ovf1 = pk_maxu(ovf1, (uint32_t)__shfl_xor((int)ovf1, 32));
@@ -1204,7 +1110,6 @@ nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ r
         if ((ovf0 & 0xFFFFu) >= OVF || (ovf0 >> 16) >= OVF) { p0[0] = p0[1] = p0[2] = qn; sig0 = qn; }
         if ((ovf1 & 0xFFFFu) >= OVF || (ovf1 >> 16) >= OVF) { p1[0] = p1[1] = p1[2] = qn; sig1 = qn; }
       }
-#endif
       if constexpr (PP::F16 && !PP::F8X) {      // a weight outside the range of this precision's operand stream (|W| >= 256): fail loudly, not plausibly
         if (auxt[AUX_FLAG] != 0.f) { const float qn = __builtin_nanf(""); p0[0] = p0[1] = p0[2] = qn; p1[0] = p1[1] = p1[2] = qn; sig0 = qn; sig1 = qn; }
       }
@@ -1217,23 +1122,12 @@ nerfmlp_fwd_kernel(const char* __restrict__ packed, const float4* __restrict__ r
           if (row_ok[1]) out_raw[row[1]] = make_float4(p1[0], p1[1], p1[2], sig1);
         }
       }
-      PH(8);
     }
 #undef RNERF_PE_KSTEP
 #undef SLAB_PREFETCH
 #undef SLAB_DONE
     tile = next_tile;
   }
-  if constexpr ((dbg & 64) != 0) {
-    if (lane == 0) out_raw[blockIdx.x * 4 + wave] = make_float4(prof_tot, prof_dma, prof_bar, prof_n);
-  }
-  if constexpr ((dbg & 256) != 0) {
-    if (lane == 0) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i) out_raw[(blockIdx.x * 4 + wave) * 3 + i] = make_float4(prof_ph[4 * i], prof_ph[4 * i + 1], prof_ph[4 * i + 2], prof_ph[4 * i + 3]);
-    }
-  }
-#undef PH
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1250,15 +1144,12 @@ constexpr int DY_L9 = 144, DY_HEADS = 152, DY_SLOTS = 153;
 // dgrad MFMA passes per product: 22 = (W_hi + W_lo) * dY_hi, i.e. exact weights times bf16-rounded gradients — the same rounding the
 // wgrad applies to dY anyway (measured worst gradient error 6.0e-3 of the tensor maximum; 3 passes: 5.1e-3 at +0.3 ms;
 // 2 = (dY_hi + dY_lo) * W_hi: 6.8e-3 at the same speed)
-#ifndef RNERF_DGRAD_PASSES
-#define RNERF_DGRAD_PASSES 22
-#endif
-constexpr int DGRAD_PASSES = RNERF_DGRAD_PASSES;
+constexpr int DGRAD_PASSES = 22;
 // Internal dgrad variant of backward F16 (not an enum rnerf_backward value): ONE MFMA per product — the weights rounded to f16 like the
 // gradients — selected when the FORWARD is the single-pass f16 one too.  The step is then one MFMA per product end to end (the arithmetic
 // north_star names); behind the f16x3 forward the F16 backward keeps its exact (hi + lo) weights (passes 22): there the rounded weights
 // would be the largest error left (gradient 4.9e-6 -> 4.1e-5 of max|g| from the default's on the bench batch), behind the f16 forward they
-// change nothing measurable (9.2e-5 both ways) and take 0.19 ms off the dgrad (1.21 -> 1.03 ms; tools/r05/t_dg1.sh).
+// change nothing measurable (9.2e-5 both ways) and take 0.19 ms off the dgrad (1.21 -> 1.03 ms; profiles/r05/README.md).
 constexpr int kBwdF16OnePass = 3;
 constexpr int kBwdBlocks = 8 * 8 + 8 * 16 * 8;   // (k-steps over n) x (8 input-feature tiles): L9 then L8..L1
 
@@ -1358,28 +1249,6 @@ template <int BWD> struct Bwd {
 __host__ __device__ constexpr size_t dy_plane_uint4(long long R, int np) { return (size_t)DY_SLOTS * np * (size_t)R * 2; }
 __host__ __device__ constexpr size_t dy_addr(int q, long long t32, int m, int h) { return (((size_t)t32 * DY_SLOTS + q) * 32 + m) * 2 + h; }     // tile-major, see sv_addr
 
-// the dY stores of one dgrad k-step one at a time (see SaveParts)
-template <bool LO8, int NP, bool ONE>
-struct DyParts {
-  uint4* dy; long long save_rows, t32_0; int q, m, h; const KOpsT<ONE>& o;
-  template <int K> __device__ __forceinline__ void part() const {
-#ifndef RNERF_DGRAD_NOSTORE
-    uint4* dst = dy + dy_addr(q, t32_0, m, h);
-    if constexpr (K == 0) stream_store(dst, o.h0);
-    if constexpr (K == 1 && !ONE) stream_store(dst + (size_t)DY_SLOTS * 64, o.h1);
-    if constexpr (LO8) {
-      uint2* dl = (uint2*)(dy + dy_plane_uint4(save_rows, 1)) + dy_addr(q, t32_0, m, h);
-      if constexpr (K == 2) stream_store8(dl, lo8_pack<true>(o.l0, LO8_SCALE_D));
-      if constexpr (K == 3 && !ONE) stream_store8(dl + (size_t)DY_SLOTS * 64, lo8_pack<true>(o.l1, LO8_SCALE_D));
-    } else if constexpr (NP == 2) {
-      uint4* dl = dst + dy_plane_uint4(save_rows, 1);
-      if constexpr (K == 2) stream_store(dl, o.l0);
-      if constexpr (K == 3 && !ONE) stream_store(dl + (size_t)DY_SLOTS * 64, o.l1);
-    }
-#endif
-  }
-};
-
 template <int BWD, bool ONE = false>
 __global__ void __launch_bounds__(256, 1)
 nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restrict__ fwd_aux, const uint4* __restrict__ saved,
@@ -1403,22 +1272,12 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
   int buf = 0;
   size_t off = 0;
   NoWork nowork;
-  constexpr int dbg = 0;
 
   if ((int)blockIdx.x < n_tiles) { issue_slab<SLAB>(packed_bwd, 0u, wave, lane); off = SLAB; }
   slab_wait_dma();
   __syncthreads();
 
   float mref = 0.f;
-  // -DRNERF_DGRAD_PROFILE (ablation build): clocks per phase of a tile, written over the head of the dy buffer (results are garbage)
-  //   0 rows + head gradients  1 first k-step operands of a layer (grad_ops(0), masks)  2 k-steps  3 layer end  4 dY_0 record
-#ifdef RNERF_DGRAD_PROFILE
-  float dprof[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  unsigned long long dlast = __builtin_amdgcn_s_memtime();
-#define DPH(K) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); dprof[K] += (float)(t_ - dlast); dlast = t_; } while (0)
-#else
-#define DPH(K) do {} while (0)
-#endif
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const bool has_next_tile = tile + (int)gridDim.x < n_tiles;
     const long long srow0 = (long long)tile * TROWS + wave * WROWS + m;
@@ -1447,7 +1306,6 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
     f32x16 acc0[8], acc1[8], prev0[8];
 
     auto dy_store = [&](int q, const KOps& o) {
-#ifndef RNERF_DGRAD_NOSTORE   /* profiling ablation */
       uint4* dst = dy + dy_addr(q, t32_0, m, h);
       stream_store(dst, o.h0);
       if constexpr (!ONE) stream_store(dst + (size_t)DY_SLOTS * 64, o.h1);
@@ -1460,7 +1318,6 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
         stream_store(dl, o.l0);
         if constexpr (!ONE) stream_store(dl + (size_t)DY_SLOTS * 64, o.l1);
       }
-#endif
     };
     // ReLU masks: one uint4 of non-zero flags per (row, half) per layer (SAVE_MASK), fetched one layer ahead
     auto mask_at = [&](int set, uint4& a, uint4& b) {
@@ -1540,9 +1397,7 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
           acc0[t][r] = a;
           if constexpr (!ONE) acc1[t][r] = b;
         }
-      DPH(0);
       layer_end();
-      DPH(3);
     }
 
     // ---- dgrad of MFMA layer 9 (Dense_10): k-steps over its 128 outputs; state masked by the saved rgb-head input
@@ -1550,11 +1405,9 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
       uint4 ma, mb;
       mask_at(8, ma, mb);
       KOps cur = grad_ops(0, true, ma, mb, nullptr);
-      DPH(1);
 #define RNERF_DG_KSTEP(S, NSTEPS, SLOT0, PREFETCH_STMT)                                                                       \
       {                                                                                                                         \
-        const DyParts<BW::LO8, BW::NP, ONE> dp{dy, save_rows, t32_0, (SLOT0) + S, m, h, cur};                                    \
-        if constexpr (!RNERF_SPREAD_STORES) dy_store((SLOT0) + S, cur);                                                         \
+        dy_store((SLOT0) + S, cur);                                                                                             \
         auto dma = [&]() { PREFETCH_STMT; };   /* issued after the first two tiles' MFMAs (an LDS-DMA instruction costs ~100 issue cycles) */ \
         if constexpr (S + 1 < NSTEPS) {                                                                                         \
           GradConv<PREC, S + 1, NEED_LO, ONE> cv(prev0[(S + 1) >> 1]);                                                                   \
@@ -1571,12 +1424,10 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
           }                                                                                                                     \
           cv.w0 = ((S + 1) >> 2) == 0 ? ma.x : (((S + 1) >> 2) == 1 ? ma.y : (((S + 1) >> 2) == 2 ? ma.z : ma.w));             \
           cv.w1 = ((S + 1) >> 2) == 0 ? mb.x : (((S + 1) >> 2) == 1 ? mb.y : (((S + 1) >> 2) == 2 ? mb.z : mb.w));             \
-          if constexpr (RNERF_SPREAD_STORES) kstep_mfma<PREC, 8, 0, S == 0, GradConv<PREC, S + 1, NEED_LO, ONE>, false, decltype(dma), DGP, KOps, DyParts<BW::LO8, BW::NP, ONE>>(acc0, acc1, cur, smem + buf * SLAB, lane, cv, dma, dp); else \
-          kstep_mfma<PREC, 8, 0, S == 0, GradConv<PREC, S + 1, NEED_LO, ONE>, false, decltype(dma), DGP>(acc0, acc1, cur, smem + buf * SLAB, lane, cv, dma); \
+          kstep_mfma<PREC, 8, 0, S == 0, GradConv<PREC, S + 1, NEED_LO, ONE>, decltype(dma), DGP>(acc0, acc1, cur, smem + buf * SLAB, lane, cv, dma); \
           cur = cv.result();                                                                                                    \
         } else {                                                                                                                \
-          if constexpr (RNERF_SPREAD_STORES) kstep_mfma<PREC, 8, 0, false, NoWork, false, decltype(dma), DGP, KOps, DyParts<BW::LO8, BW::NP, ONE>>(acc0, acc1, cur, smem + buf * SLAB, lane, nowork, dma, dp); else \
-          kstep_mfma<PREC, 8, 0, false, NoWork, false, decltype(dma), DGP>(acc0, acc1, cur, smem + buf * SLAB, lane, nowork, dma);  \
+          kstep_mfma<PREC, 8, 0, false, NoWork, decltype(dma), DGP>(acc0, acc1, cur, smem + buf * SLAB, lane, nowork, dma);         \
         }                                                                                                                       \
         SLAB_DONE();                                                                                                            \
       }
@@ -1587,9 +1438,7 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
         RNERF_DG_KSTEP(4, 8, DY_L9, SLAB_PREFETCH(true)) RNERF_DG_KSTEP(5, 8, DY_L9, SLAB_PREFETCH(true))
         RNERF_DG_KSTEP(6, 8, DY_L9, SLAB_PREFETCH(true)) RNERF_DG_KSTEP(7, 8, DY_L9, SLAB_PREFETCH(true))
       }
-      DPH(2);
       layer_end();
-      DPH(3);
     }
 
     // ---- dgrad of MFMA layers 8..1: dY_l = (dX_{l+1} [+ d sigma * w_sigma for l = 7]) * 1[X_{l+1} > 0]  (no mask for the bottleneck l = 8)
@@ -1603,7 +1452,6 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
       mask_at(l - 1, nma, nmb);
       KOps cur = grad_ops(0, true, ma, mb, wadd);
       const int slot0 = 16 * l;
-      DPH(1);
 #define RNERF_DG_PF(S) do { if ((S) == 15 && l == 1) { if (has_next_tile) off = 0; SLAB_PREFETCH(has_next_tile); } else SLAB_PREFETCH(true); } while (0)
       RNERF_DG_KSTEP(0, 16, slot0, RNERF_DG_PF(0)) RNERF_DG_KSTEP(1, 16, slot0, RNERF_DG_PF(1)) RNERF_DG_KSTEP(2, 16, slot0, RNERF_DG_PF(2))
       RNERF_DG_KSTEP(3, 16, slot0, RNERF_DG_PF(3)) RNERF_DG_KSTEP(4, 16, slot0, RNERF_DG_PF(4)) RNERF_DG_KSTEP(5, 16, slot0, RNERF_DG_PF(5))
@@ -1612,9 +1460,7 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
       RNERF_DG_KSTEP(12, 16, slot0, RNERF_DG_PF(12)) RNERF_DG_KSTEP(13, 16, slot0, RNERF_DG_PF(13)) RNERF_DG_KSTEP(14, 16, slot0, RNERF_DG_PF(14))
       RNERF_DG_KSTEP(15, 16, slot0, RNERF_DG_PF(15))
 #undef RNERF_DG_PF
-      DPH(2);
       layer_end();
-      DPH(3);
     }
 #undef RNERF_DG_KSTEP
 
@@ -1624,7 +1470,6 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
       const KOps o = grad_ops(s, true, nma, nmb, nullptr);
       dy_store(s, o);
     }
-    DPH(4);
 #undef SLAB_PREFETCH
 #undef SLAB_DONE
   }
@@ -1634,14 +1479,6 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
     if (lane == 0 && mref > 0.f)
       atomicMax((unsigned int*)((float*)(dy + dy_plane_uint4(save_rows, BW::NP)) + save_rows), __builtin_bit_cast(unsigned int, mref));
   }
-#ifdef RNERF_DGRAD_PROFILE
-  if (lane == 0) {
-    float4* pr = (float4*)dy + (blockIdx.x * 4 + wave) * 2;
-    pr[0] = make_float4(dprof[0], dprof[1], dprof[2], dprof[3]);
-    pr[1] = make_float4(dprof[4], dprof[5], dprof[6], dprof[7]);
-  }
-#endif
-#undef DPH
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1809,19 +1646,10 @@ template <int KT, int NT> struct WgTrShape {
   static constexpr int TK = KT / WK, TN = NTR / WN;
   static_assert(WK * TK == KT && WN * TN == NTR && WK * WN <= 8 && (!EXTRA || (TK == 2 && WN == 2)), "tile split");
 };
-#ifndef RNERF_WGTR_LATE_DMA
-#define RNERF_WGTR_LATE_DMA 0      /* round 6: launched ALONE it pays (tools/r06/ab_wgrad.py: f16x3 wgrad 2.008 / 2.010 -> 1.987 / 1.973 ms), in the STEP — the next batch's \
-                                      march co-resident on the same SIMDs — it does not (tools/r06/ab_step.py, three alternating pairs: 6.352 / 6.352 / 6.355 ms with it, 6.348 / 6.319 / 6.319 without): off */
-#endif
-#ifndef RNERF_WGTR_NCH
-#define RNERF_WGTR_NCH 2      /* n-tiles of B fragments fetched at a time when the A side is resident */
-#endif
+constexpr int WGTR_NCH = 2;      // n-tiles of B fragments fetched at a time when the A side is resident
 template <int NP> constexpr int wgtr_nbuf() { return NP == 2 ? 4 : 8; }       // ring depth: what fits 160 KiB
 template <int NP> constexpr int wgtr_lds_bytes() { return wgtr_nbuf<NP>() * ((10 + 8) * NP + 1) * 1024; }       // largest job: 10 k-tiles + 8 n-tiles
 
-#if defined(RNERF_WGTR_ABL) && (RNERF_WGTR_ABL & 2)   /* profiling ablation: no LDS operand reads */
-__device__ __forceinline__ half8 tr_read8(const char* p) { const _Float16 v = (_Float16)(float)((size_t)p & 7); return half8{v, v, v, v, v, v, v, v}; }
-#else
 __device__ __forceinline__ half8 tr_read8(const char* p) {      // rows k .. k+3 at p, rows k+4 .. k+7 at p + 256 (4 rows x 64 B)
   typedef short short4v __attribute__((ext_vector_type(4)));
   typedef short short8v __attribute__((ext_vector_type(8)));
@@ -1830,12 +1658,7 @@ __device__ __forceinline__ half8 tr_read8(const char* p) {      // rows k .. k+3
   const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4*)(p + 256));
   return __builtin_bit_cast(half8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
-#endif
-#if defined(RNERF_WGTR_ABL) && (RNERF_WGTR_ABL & 1)   /* profiling ablation: the wgrad without its MFMAs (results are garbage) */
-__device__ __forceinline__ f32x16 mfma_h8(const half8 a, const half8 b, f32x16 c) { c[0] += (float)a[0] * (float)b[0]; return c; }
-#else
 __device__ __forceinline__ f32x16 mfma_h8(const half8 a, const half8 b, const f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-#endif
 template <int N> __device__ __forceinline__ void wait_vmcnt() {
   __builtin_amdgcn_s_waitcnt(0x0F70 | (N & 15) | ((N >> 4) << 14));
   asm volatile("" ::: "memory");
@@ -1924,12 +1747,11 @@ __device__ __forceinline__ void wgrad_body_tr(const uint4* __restrict__ saved, c
       if (wave == 0) wait_vmcnt<(AHEAD - 1) * (NDMA + 1)>(); else
       wait_vmcnt<(AHEAD - 1) * NDMA>();                         // this wave's part of step s has landed (the later steps may be in flight)
       __syncthreads();                                          // ... everybody's has, and everybody is done with the ring slot of step s - 1
-      // An LDS-DMA instruction costs ~100 issue cycles and a wave issues NDMA of them per step.  Right behind the barrier all eight waves
-      // would do that at once, with the matrix pipe idle: the second wave of every SIMD (waves 4..7) issues its share after its first chunk
-      // of MFMAs instead, so that one wave's DMA issue overlaps its partner's MFMAs (RNERF_WGTR_LATE_DMA; the slot written is the one of
-      // step s - 1, free since the barrier)
-      const bool dma_late = RNERF_WGTR_LATE_DMA && wave >= 4 && active;
-      if (!dma_late) issue(s + AHEAD);
+      // Every wave issues its DMA share (NDMA LDS-DMA instructions, ~100 issue cycles each) right behind the barrier.  The second wave of
+      // every SIMD issuing it after its first chunk of MFMAs instead pays launched alone (f16x3 wgrad 2.008 / 2.010 -> 1.987 / 1.973 ms) but
+      // not in the step, where the next batch's march shares those SIMDs (6.352 / 6.352 / 6.355 ms with it, 6.348 / 6.319 / 6.319 without;
+      // DESIGN.md section 3.3, profiles/r06/ab_step_late_dma.txt)
+      issue(s + AHEAD);
       if (active) {
         const char* ring0 = smem + (s & (WGTR_NBUF - 1)) * STEP_BYTES;
         const char* ring = ring0 + lane_off;
@@ -1937,7 +1759,7 @@ __device__ __forceinline__ void wgrad_body_tr(const uint4* __restrict__ saved, c
         const half8 sc8 = {(_Float16)(s0.x * inv_mref), (_Float16)(s0.y * inv_mref), (_Float16)(s0.z * inv_mref), (_Float16)(s0.w * inv_mref),
                            (_Float16)(s1.x * inv_mref), (_Float16)(s1.y * inv_mref), (_Float16)(s1.z * inv_mref), (_Float16)(s1.w * inv_mref)};
         // Operands are fetched and consumed in chunks so that the live set beside the TK x TN accumulators stays small enough for
-        // RNERF_WGRAD_VGPRS without spilling: the smaller operand side stays resident for the step, the other side streams through in
+        // WGRAD_VGPRS without spilling: the smaller operand side stays resident for the step, the other side streams through in
         // chunks (A fragments one k-tile at a time when TK > TN, else B fragments NCH n-tiles at a time).
         half8 beh, bel;
         if constexpr (SH::EXTRA) {
@@ -1959,7 +1781,7 @@ __device__ __forceinline__ void wgrad_body_tr(const uint4* __restrict__ saved, c
         // bias row: wave (wk, wn) owns it for n-tile wn TN + wk, wk < TN (the 9th n-tile of the Dense_9 + sigma job has no owner: the
         // sigma bias comes out of the rgb-head job, which reads the same head-gradient slot).  A B fragment holds, per lane, 8 rows of one
         // column and sc8 the scales of the same 8 rows: four v_dot2_f32_f16 per fragment instead of an MFMA with a one-row A operand and
-        // a 16-register accumulator (the kernel has to stay within RNERF_WGRAD_VGPRS).
+        // a 16-register accumulator (the kernel has to stay within WGRAD_VGPRS).
         auto dot8 = [&](const half8& x, float c) -> float {
           typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 #pragma unroll
@@ -1991,12 +1813,11 @@ __device__ __forceinline__ void wgrad_body_tr(const uint4* __restrict__ saved, c
 #pragma unroll
               for (int j = 0; j < TN; ++j) acc[i][j] = mfma_h8(al, bh[j], acc[i][j]);
             }
-            if (i == 0 && dma_late) issue(s + AHEAD);
           }
 #pragma unroll
           for (int j = 0; j < TN; ++j) bias_row(j, bh[j], bl[j]);
         } else {                            // A resident, B streams in chunks of NCH n-tiles
-          constexpr int NCH = RNERF_WGTR_NCH < TN ? RNERF_WGTR_NCH : TN;
+          constexpr int NCH = WGTR_NCH < TN ? WGTR_NCH : TN;
           static_assert(TN % NCH == 0, "n-tile chunks");
           half8 ah[TK], al[TK];
 #pragma unroll
@@ -2022,7 +1843,6 @@ __device__ __forceinline__ void wgrad_body_tr(const uint4* __restrict__ saved, c
             }
 #pragma unroll
             for (int jj = 0; jj < NCH; ++jj) bias_row(c * NCH + jj, bh[jj], bl[jj]);
-            if (c == 0 && dma_late) issue(s + AHEAD);
           }
           if constexpr (SH::EXTRA) { ae_h = wn ? ah[1] : ah[0]; if constexpr (NP == 2) ae_l = wn ? al[1] : al[0]; }
         }
@@ -2074,18 +1894,12 @@ template <int KT, int NT> struct WgTr8 {
   static constexpr int NBLK = NHI + NLX + NLD, NDMA = (NBLK + 7) / 8, STEP_BYTES = (NBLK + 1) * 1024;
   static constexpr int LOX = NHI * 1024, LOD = (NHI + NLX) * 1024, SCALES = NBLK * 1024;
 };
-#ifndef RNERF_WGTR8_NBUF
-#define RNERF_WGTR8_NBUF 4
-#endif
-constexpr int wgtr8_lds_bytes() { return RNERF_WGTR8_NBUF * WgTr8<10, 8>::STEP_BYTES; }      // largest job: 10 k-tiles + 8 n-tiles
-#if defined(RNERF_WGTR_ABL) && (RNERF_WGTR_ABL & 2)
-__device__ __forceinline__ int2v tr_read8b(const char* p) { const int v = (int)((size_t)p & 7); return int2v{v, v}; }
-#else
+constexpr int WGTR8_NBUF = 4;      // ring depth (5 for the smaller steps measured slower: DESIGN.md section 3.3)
+constexpr int wgtr8_lds_bytes() { return WGTR8_NBUF * WgTr8<10, 8>::STEP_BYTES; }      // largest job: 10 k-tiles + 8 n-tiles
 __device__ __forceinline__ int2v tr_read8b(const char* p) {
   typedef __attribute__((address_space(3))) int2v lds_int2;
   return __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_int2*)p);
 }
-#endif
 
 template <int KT, int NT>
 __device__ __forceinline__ void wgrad_body_tr8(const uint4* __restrict__ saved, const uint4* __restrict__ dy, long long R, float* __restrict__ pg,
@@ -2094,7 +1908,7 @@ __device__ __forceinline__ void wgrad_body_tr8(const uint4* __restrict__ saved, 
   using L8 = WgTr8<KT, NT>;
   constexpr int TK = SH::TK, TN = SH::TN;
   constexpr int NHI = L8::NHI, NBLK = L8::NBLK, NDMA = L8::NDMA, STEP_BYTES = L8::STEP_BYTES;
-  constexpr int WGTR_NBUF = RNERF_WGTR8_NBUF, AHEAD = WGTR_NBUF - 1;
+  constexpr int WGTR_NBUF = WGTR8_NBUF, AHEAD = WGTR_NBUF - 1;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wk = wave / SH::WN, wn = wave % SH::WN;
@@ -2170,8 +1984,7 @@ __device__ __forceinline__ void wgrad_body_tr8(const uint4* __restrict__ saved, 
       if (wave == 0) wait_vmcnt<(AHEAD - 1) * (NDMA + 1)>(); else
       wait_vmcnt<(AHEAD - 1) * NDMA>();
       __syncthreads();
-      const bool dma_late = RNERF_WGTR_LATE_DMA && wave >= 4 && active;      // see wgrad_body_tr
-      if (!dma_late) issue(s + AHEAD);
+      issue(s + AHEAD);      // see wgrad_body_tr
       if (active) {
         const char* ring0 = smem + (s % WGTR_NBUF) * STEP_BYTES;
         const char* ring = ring0 + lane_off;
@@ -2220,12 +2033,11 @@ __device__ __forceinline__ void wgrad_body_tr8(const uint4* __restrict__ saved, 
             for (int j = 0; j < TN; ++j) acc[i][j] = mfma_h8(ah, bl[j], acc[i][j]);
 #pragma unroll
             for (int j = 0; j < TN; ++j) acc[i][j] = mfma_h8(al, bh[j], acc[i][j]);
-            if (i == 0 && dma_late) issue(s + AHEAD);
           }
 #pragma unroll
           for (int j = 0; j < TN; ++j) bias_row(j, bh[j], bl[j]);
         } else {                            // A resident, B streams in chunks of NCH n-tiles
-          constexpr int NCH = RNERF_WGTR_NCH < TN ? RNERF_WGTR_NCH : TN;
+          constexpr int NCH = WGTR_NCH < TN ? WGTR_NCH : TN;
           static_assert(TN % NCH == 0, "n-tile chunks");
           half8 ah[TK], al[TK];
 #pragma unroll
@@ -2249,7 +2061,6 @@ __device__ __forceinline__ void wgrad_body_tr8(const uint4* __restrict__ saved, 
               for (int jj = 0; jj < NCH; ++jj) acc[i][c * NCH + jj] = mfma_h8(al[i], bh[jj], acc[i][c * NCH + jj]);
 #pragma unroll
             for (int jj = 0; jj < NCH; ++jj) bias_row(c * NCH + jj, bh[jj], bl[jj]);
-            if (c == 0 && dma_late) issue(s + AHEAD);
           }
           if constexpr (SH::EXTRA) { ae_h = wn ? ah[1] : ah[0]; ae_l = wn ? al[1] : al[0]; }
         }
@@ -2290,17 +2101,12 @@ __device__ __forceinline__ void wgrad_body_tr8(const uint4* __restrict__ saved, 
 // At most 224 VGPRs per wave: two of these waves per SIMD then leave 64 registers — one wave of the march kernel — on every SIMD, so
 // the next batch's march (a latency-bound chain that needs a wave slot on every CU, no LDS) can be co-resident with this HBM-paced kernel
 // instead of waiting for whole CUs to drain.
-#ifndef RNERF_WGRAD_VGPRS
-#define RNERF_WGRAD_VGPRS 112   /* the attribute counts half of the unified VGPR + AGPR file on gfx90a+: 112 -> 224 registers */
-#endif
+constexpr int WGRAD_VGPRS = 112;      // the attribute counts half of the unified VGPR + AGPR file on gfx90a+: 112 -> 224 registers
 template <int NP>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(RNERF_WGRAD_VGPRS)))
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(WGRAD_VGPRS)))
 nerfmlp_wgrad_tr_kernel(const uint4* __restrict__ saved, const uint4* __restrict__ dy, long long R, float* __restrict__ workspace, const WgradTable tab,
                         long long* __restrict__ trace) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-#if defined(RNERF_WGTR_PRIO) && RNERF_WGTR_PRIO > 0
-  __builtin_amdgcn_s_setprio(RNERF_WGTR_PRIO);      // above the co-resident march wave in the SIMD's issue arbitration
-#endif
   if (trace && threadIdx.x == 0) trace[2 * blockIdx.x] = (long long)__builtin_amdgcn_s_memrealtime();
   int j = 0;
   while ((int)blockIdx.x >= tab.wg0[j + 1]) ++j;
@@ -2321,7 +2127,7 @@ nerfmlp_wgrad_tr_kernel(const uint4* __restrict__ saved, const uint4* __restrict
   __builtin_trap();
 }
 
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(RNERF_WGRAD_VGPRS)))
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(WGRAD_VGPRS)))
 nerfmlp_wgrad_tr8_kernel(const uint4* __restrict__ saved, const uint4* __restrict__ dy, long long R, float* __restrict__ workspace, const WgradTable tab,
                          long long* __restrict__ trace) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -3470,45 +3276,11 @@ static size_t save_payload_bytes(long long padded, bool with_lo) {
   return (size_t)(SAVE_TOTAL + (with_lo ? SAVE_SLOTS : 0)) * (size_t)padded * 2 * sizeof(uint4);
 }
 
-static int mlp_debug_flags() {
-  static int v = -1;
-  if (v < 0) { const char* e = RNERF_ENV("RNERF_MLP_DEBUG"); v = e ? atoi(e) : 0; }
-  return v;
-}
-
-template <int PREC, int DBG, int TRAIN = 0>
-static int launch_fwd_dbg(const void* packed, const float* rows_pd, const float* rows_dr, const int32_t* node_of_sample, int32_t B,
-                          long long total_rows, float* out_raw, hipStream_t st, void* save = nullptr, int max_wg = 0, const float* gate = nullptr,
-                          int gate_skip_if = 0);
-
-template <int PREC>
-static int launch_fwd(const void* packed, const float* rows_pd, const float* rows_dr, const int32_t* node_of_sample, int32_t B,
-                      long long total_rows, float* out_raw, hipStream_t st, int max_wg, const float* gate = nullptr, int gate_skip_if = 0) {
-#ifdef RNERF_MLP_ABLATE
-  switch (mlp_debug_flags()) {
-    case 1: return launch_fwd_dbg<PREC, 1>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg);
-    case 2: return launch_fwd_dbg<PREC, 2>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg);
-    case 3: return launch_fwd_dbg<PREC, 3>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg);
-    case 4: return launch_fwd_dbg<PREC, 4>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg);
-    case 5: return launch_fwd_dbg<PREC, 5>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg);
-    case 8: return launch_fwd_dbg<PREC, 8>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg);
-    case 13: return launch_fwd_dbg<PREC, 13>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg);
-    case 16: return launch_fwd_dbg<PREC, 16>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg);
-    case 48: return launch_fwd_dbg<PREC, 48>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg);
-    case 128: return launch_fwd_dbg<PREC, 128>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg);
-    case 64: return launch_fwd_dbg<PREC, 64>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg);
-    case 32: return launch_fwd_dbg<PREC, 32>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg);
-    case 29: return launch_fwd_dbg<PREC, 29>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg);
-    case 256: return launch_fwd_dbg<PREC, 256>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg);
-    default: break;
-  }
-#endif
-  return launch_fwd_dbg<PREC, 0>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg, gate, gate_skip_if);
-}
-
-template <int PREC, int DBG, int TRAIN>
-static int launch_fwd_dbg(const void* packed, const float* rows_pd, const float* rows_dr, const int32_t* node_of_sample, int32_t B,
-                      long long total_rows, float* out_raw, hipStream_t st, void* save, int max_wg, const float* gate, int gate_skip_if) {
+// MODE: 0 = the pass, 512 = the range-safe second pass (REDO in nerfmlp_fwd_kernel); TRAIN: see nerfmlp_fwd_kernel
+template <int PREC, int MODE = 0, int TRAIN = 0>
+static int launch_fwd_mode(const void* packed, const float* rows_pd, const float* rows_dr, const int32_t* node_of_sample, int32_t B,
+                           long long total_rows, float* out_raw, hipStream_t st, void* save = nullptr, int max_wg = 0, const float* gate = nullptr,
+                           int gate_skip_if = 0) {
   using PP = Prec<PREC>;
   const int n_tiles = (int)((total_rows + 255) / 256);
   int dev = 0, cus = 0;
@@ -3519,7 +3291,7 @@ static int launch_fwd_dbg(const void* packed, const float* rows_pd, const float*
   // waves, so a launch that cannot fill the chip with 256-row tiles (a 512-ray shard's coarse level: 128 tiles on 256 CUs; both levels of a
   // 128-ray one) finishes sooner on twice as many CUs with half the work each.  (Beyond one round the 256-row tiles' better reuse of the
   // weight stream wins.)  RNERF_FWD_HALF_TILES=0 switches it off (A/B).
-  if constexpr (DBG == 0 && (PREC == RNERF_PREC_F16X3 || PREC == RNERF_PREC_F16F8)) {
+  if constexpr (MODE == 0 && (PREC == RNERF_PREC_F16X3 || PREC == RNERF_PREC_F16F8)) {
     static const bool half_ok = [] { const char* e = RNERF_ENV("RNERF_FWD_HALF_TILES"); return !(e && e[0] == '0'); }();
     if (half_ok && 2 * n_tiles <= lim) {
       const size_t lds1 = 2 * (size_t)PP::SLAB;
@@ -3539,7 +3311,7 @@ static int launch_fwd_dbg(const void* packed, const float* rows_pd, const float*
   const size_t lds = 2 * (size_t)PP::SLAB + 4 * 32768;
   static DeviceOnce attr_set;
   if (attr_set.need()) {
-    RNERF_CHECK_HIP(hipFuncSetAttribute((const void*)nerfmlp_fwd_kernel<PREC, DBG, TRAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RNERF_CHECK_HIP(hipFuncSetAttribute((const void*)nerfmlp_fwd_kernel<PREC, MODE, TRAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set.set();
   }
   int* tileq = nullptr;
@@ -3547,11 +3319,17 @@ static int launch_fwd_dbg(const void* packed, const float* rows_pd, const float*
     tileq = (int*)((char*)save + save_payload_bytes((long long)n_tiles * 256, TRAIN >= 2));
     RNERF_CHECK_HIP(hipMemsetAsync(tileq, 0, sizeof(int), st));
   }
-  hipLaunchKernelGGL((nerfmlp_fwd_kernel<PREC, DBG, TRAIN>), dim3(grid), dim3(256), lds, st, (const char*)packed, (const float4*)rows_pd,
+  hipLaunchKernelGGL((nerfmlp_fwd_kernel<PREC, MODE, TRAIN>), dim3(grid), dim3(256), lds, st, (const char*)packed, (const float4*)rows_pd,
                      (const float4*)rows_dr, node_of_sample, B, total_rows, n_tiles, (float4*)out_raw, (uint4*)save,
                      (long long)n_tiles * 256, tileq, gate, gate_skip_if);
   RNERF_CHECK_LAUNCH();
   return RNERF_OK;
+}
+
+template <int PREC>
+static int launch_fwd(const void* packed, const float* rows_pd, const float* rows_dr, const int32_t* node_of_sample, int32_t B,
+                      long long total_rows, float* out_raw, hipStream_t st, int max_wg, const float* gate = nullptr, int gate_skip_if = 0) {
+  return launch_fwd_mode<PREC>(packed, rows_pd, rows_dr, node_of_sample, B, total_rows, out_raw, st, nullptr, max_wg, gate, gate_skip_if);
 }
 
 extern "C" int rnerf_nerfmlp_forward(const void* packed, int precision, const float* rows_pd, const float* rows_dr,
@@ -3571,22 +3349,22 @@ extern "C" int rnerf_nerfmlp_forward(const void* packed, int precision, const fl
     // as NaN — an activation above f16's 65504, a weight >= 256 —, nothing else touched; without such a row it reads out_raw once and ends
     case RNERF_PREC_F16X3:
       RNERF_TRY_(launch_fwd<RNERF_PREC_F16X3>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, max_workgroups));
-      return launch_fwd_dbg<RNERF_PREC_BF16X3, 512>((const char*)packed + safe_stream_offset(precision), rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, nullptr, max_workgroups);
+      return launch_fwd_mode<RNERF_PREC_BF16X3, 512>((const char*)packed + safe_stream_offset(precision), rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, nullptr, max_workgroups);
     case RNERF_PREC_F16X2:
       RNERF_TRY_(launch_fwd<RNERF_PREC_F16X2>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, max_workgroups));
-      return launch_fwd_dbg<RNERF_PREC_BF16X3, 512>((const char*)packed + safe_stream_offset(precision), rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, nullptr, max_workgroups);
+      return launch_fwd_mode<RNERF_PREC_BF16X3, 512>((const char*)packed + safe_stream_offset(precision), rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, nullptr, max_workgroups);
     case RNERF_PREC_F16F8: {
       // the f16f8 launch steps aside when its pack kernel flagged a weight outside the range of the 2^14-scaled stream (|W| >= 3.99); the f16x3
       // launch behind it (its stream sits in the same packed buffer) runs only then: a fallback per launch, decided on the device
       const float* flag = (const float*)((const char*)packed + Prec<RNERF_PREC_F16F8>::STREAM_BYTES) + AUX_FLAG;
       RNERF_TRY_(launch_fwd<RNERF_PREC_F16F8>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, max_workgroups, flag, 1));
       RNERF_TRY_(launch_fwd<RNERF_PREC_F16X3>((const char*)packed + kF8Fallback, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, max_workgroups, flag, 0));
-      return launch_fwd_dbg<RNERF_PREC_BF16X3, 512>((const char*)packed + safe_stream_offset(precision), rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, nullptr, max_workgroups);
+      return launch_fwd_mode<RNERF_PREC_BF16X3, 512>((const char*)packed + safe_stream_offset(precision), rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, nullptr, max_workgroups);
     }
     case RNERF_PREC_BF16X3: return launch_fwd<RNERF_PREC_BF16X3>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, max_workgroups);
     case RNERF_PREC_F16:
       RNERF_TRY_(launch_fwd<RNERF_PREC_F16>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, max_workgroups));
-      return launch_fwd_dbg<RNERF_PREC_BF16X3, 512>((const char*)packed + safe_stream_offset(precision), rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, nullptr, max_workgroups);
+      return launch_fwd_mode<RNERF_PREC_BF16X3, 512>((const char*)packed + safe_stream_offset(precision), rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, nullptr, max_workgroups);
     default: return launch_fwd<RNERF_PREC_BF16>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, max_workgroups);
   }
 }
@@ -3625,15 +3403,11 @@ extern "C" int rnerf_nerfmlp_forward_train(const void* packed, int precision, co
                   "rnerf_nerfmlp_forward_train: buffers must be 16-byte aligned");
   const long long total = (long long)S * B;
   hipStream_t st = (hipStream_t)stream;
-#ifdef RNERF_MLP_ABLATE      /* RNERF_MLP_DEBUG=256: per-phase clocks of the training forward (hi + lo saves) */
-  if (backward == RNERF_BWD_F16X2 && mlp_debug_flags() == 256)
-    return launch_fwd_dbg<RNERF_PREC_F16X3, 256, 2>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, save, max_workgroups);
-#endif
-  if (backward == RNERF_BWD_F16X2) return launch_fwd_dbg<RNERF_PREC_F16X3, 0, 2>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, save, max_workgroups);
-  if (backward == RNERF_BWD_F16X3_LO8) return launch_fwd_dbg<RNERF_PREC_F16X3, 0, 3>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, save, max_workgroups);
-  if (precision == RNERF_PREC_BF16X3) return launch_fwd_dbg<RNERF_PREC_BF16X3, 0, 1>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, save, max_workgroups);
-  if (precision == RNERF_PREC_F16) return launch_fwd_dbg<RNERF_PREC_F16, 0, 1>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, save, max_workgroups);
-  return launch_fwd_dbg<RNERF_PREC_F16X3, 0, 1>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, save, max_workgroups);
+  if (backward == RNERF_BWD_F16X2) return launch_fwd_mode<RNERF_PREC_F16X3, 0, 2>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, save, max_workgroups);
+  if (backward == RNERF_BWD_F16X3_LO8) return launch_fwd_mode<RNERF_PREC_F16X3, 0, 3>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, save, max_workgroups);
+  if (precision == RNERF_PREC_BF16X3) return launch_fwd_mode<RNERF_PREC_BF16X3, 0, 1>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, save, max_workgroups);
+  if (precision == RNERF_PREC_F16) return launch_fwd_mode<RNERF_PREC_F16, 0, 1>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, save, max_workgroups);
+  return launch_fwd_mode<RNERF_PREC_F16X3, 0, 1>(packed, rows_pd, rows_dr, node_of_sample, B, total, out_raw, st, save, max_workgroups);
 }
 
 extern "C" size_t rnerf_nerfmlp_bwd_packed_bytes(void) { return (size_t)kBwdBlocks * 2 * 1024; }
@@ -3681,7 +3455,7 @@ static int launch_dgrad(const void* packed_bwd, const float* fwd_aux, const void
   }
   const long long R = (long long)n_tiles * 256;
   if (Bwd<BWD>::F16 && zero_ref) RNERF_CHECK_HIP(hipMemsetAsync(nerfmlp_dgrad_scale_ref(BWD == kBwdF16OnePass ? RNERF_BWD_F16 : BWD, dy, rows), 0, 4 * sizeof(float), st));
-  // Few rows: 128-row tiles when they all fit one round (see launch_fwd_dbg) — unless the caller runs another level's dgrad beside this one
+  // Few rows: 128-row tiles when they all fit one round (see launch_fwd_mode) — unless the caller runs another level's dgrad beside this one
   // (allow_half = false): two kernels that each own whole CUs then share the chip, and with twice the workgroups of half the work the
   // step measures the same or slower (512 rays, levels side by side: 2.05 -> 2.09 ms; alone, a 256-ray single-level step: 1.17 -> 1.12 ms).
   if constexpr (BWD == RNERF_BWD_F16X2 || BWD == RNERF_BWD_F16 || BWD == kBwdF16OnePass || BWD == RNERF_BWD_F16X3_LO8) {
@@ -3771,8 +3545,7 @@ static size_t build_wgrad_table(int cus, WgradTable& t, bool legacy, int mult = 
     total += cost[n];
   }
   t.n = n;
-  static const int mult_env = RNERF_ENV("RNERF_WGRAD_MULT") ? atoi(RNERF_ENV("RNERF_WGRAD_MULT")) : 0;
-  const int budget = (mult_env > 0 ? mult_env : (mult > 0 ? mult : (legacy ? 4 : 2))) * cus;
+  const int budget = (mult > 0 ? mult : (legacy ? 4 : 2)) * cus;
   size_t off = 0;
   int wg = 0;
   for (int i = 0; i < n; ++i) {
@@ -3798,7 +3571,7 @@ static int device_cus() {
 // tr_small: the transposing body's table for a FEW rows (<= kWgradSmallRows: both levels of a 128-ray shard of the reference's default
 // batch): one round of workgroups instead of two — every workgroup writes its whole partial dW block whatever its share of the rows, and
 // with < 100 rows per workgroup that fixed cost is the kernel (128 rays: 1.29 -> 1.23 ms per step; from 32 768 rows on — the coarse level of
-// a 512-ray batch — two rounds are faster: 2.14 against 2.18 ms, tools/r04/wgrad_mult.sh).  Smaller than `tr` in workgroups and partials:
+// a 512-ray batch — two rounds are faster: 2.14 against 2.18 ms in round 4; profiles/r04/small_batches.txt).  Smaller than `tr` in workgroups and partials:
 // the workspace size is unchanged.
 constexpr long long kWgradSmallRows = 24576;
 struct WgradTables { WgradTable legacy, tr, tr_small; size_t partial_floats; int max_wgs; };

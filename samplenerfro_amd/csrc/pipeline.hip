@@ -167,17 +167,6 @@ __global__ void __launch_bounds__(256) bkgd_dirs_kernel(const float4* __restrict
   }
 }
 
-// (experiment, -DRNERF_TAIL_DELAY_US=<n>, default 0 = not launched)
-// One wave that does nothing for `ticks` of the 100 MHz real-time counter.  Issued on the tail stream ahead of the co-resident kernels:
-// streams express "after X completed", not "after X has STARTED", so without it the small kernels race the NerfMLP wgrad for the CUs at
-// the fork, and wherever their waves land first the wgrad's 8-wave workgroup (2 x 216 registers per SIMD, 148 KiB of LDS) has to wait
-// for them to drain.  A few tens of microseconds later the wgrad's workgroups are resident everywhere and the co-resident waves only
-// take what it leaves free.
-__global__ void spin_kernel(long long ticks) {
-  const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
-  while ((long long)__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
-}
-
 // trans_rgb_bkgd = trans * rgb_behind (rnerf/models.py:520-524)
 __global__ void __launch_bounds__(256) bd_cut_mul_kernel(const float* __restrict__ trans, const float* __restrict__ behind, int B,
                                                          float* __restrict__ out) {
@@ -457,10 +446,6 @@ extern "C" int rnerf_forward(const rnerf_model* m, const float* origins, const f
 
 // ---- training --------------------------------------------------------------------------------------------------------------------
 namespace rnerf {
-#ifndef RNERF_TAIL_DELAY_US
-#define RNERF_TAIL_DELAY_US 0
-#endif
-constexpr long long kTailDelayTicks = 100LL * RNERF_TAIL_DELAY_US;      // s_memrealtime counts at 100 MHz
 static inline bool co_requested(const rnerf_train_cfg* c) { return c->aux_stream && c->coresident_bkgd_wgrad; }
 // hierarchical models with an aux stream: the two levels' backward passes side by side when together they are at most two rounds of row
 // tiles (see rnerf_train_forward_backward); also decides whether the workspace carries the coarse level's own dY / d raw / wgrad scratch
@@ -644,7 +629,7 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
   const double mse_scale = 2.0 / (3.0 * B);
   if (!aux) RNERF_CHECK_HIP(hipMemsetAsync(grads, 0, (size_t)(n_theta + 8) * sizeof(float), st));
   // The next batch's march on the side stream, forked from `stream` at the call.  With beside_wgrad it is issued right before the LARGEST
-  // wgrad of the step (the fine level's when there is one): the wgrad keeps 64 registers free on every SIMD (RNERF_WGRAD_VGPRS), so the
+  // wgrad of the step (the fine level's when there is one): the wgrad keeps 64 registers free on every SIMD (WGRAD_VGPRS in mlp.hip), so the
   // march's waves are co-resident with it and the whole march hides behind that HBM-paced kernel.
   auto march_next = [&]() -> int {
     RNERF_CHECK_ARG(next->origins && next->viewdirs && next->path_pd && next->path_dr && next->side_stream, "rnerf_train_forward_backward: incomplete rnerf_prefetch");
@@ -663,8 +648,7 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
   // rounds: beyond that the kernels' static tile striding is delayed on the CUs the other level took first and the step gets SLOWER
   // (profiles/r04/levels_side_by_side.txt: 512 rays 2.28 -> 2.18 ms, 128 rays 1.50 -> 1.33; 1024 rays 3.36 -> 3.45, 4096 rays 11.9 -> 12.4).
   const bool split_levels = levels_side_by_side(m, c, B);
-  static const bool bk_early_env = RNERF_ENV("RNERF_BKGD_BWD_EARLY") ? atoi(RNERF_ENV("RNERF_BKGD_BWD_EARLY")) != 0 : true;
-  const bool bk_early = split_levels && bk_early_env && !(aux && c->coresident_bkgd_wgrad);
+  const bool bk_early = split_levels && !(aux && c->coresident_bkgd_wgrad);
   void* bk2 = nullptr;      // the third stream, when the background backward went there
   float* d_raw_c = split_levels ? t.d_raw_c : t.d_raw;
   void* dy_c = split_levels ? t.dy_c : t.dy;
@@ -677,7 +661,7 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
       RNERF_TRY(rnerf_fork(stream, aux));
       if (bk_early) {      // d loss / d background is final (both compositing backwards have run): its whole backward goes beside the NerfMLP
         // chains — on the third stream when there is one (nothing waits behind it), else in front of the coarse level's on the aux stream.
-        // (Measured, tools/r04/env_ab.sh RNERF_NO_AUX2_STREAM: 256 rays 1.48 -> 1.39 ms, 512 rays the same, 128 rays 1.09 -> 1.11: with a
+        // (Measured, profiles/r04/small_batches.txt: 256 rays 1.48 -> 1.39 ms, 512 rays the same, 128 rays 1.09 -> 1.11: with a
         // quarter of the chip's tiles the coarse chain is not what the step waits for, and the third stream only adds its fork / join.)
         const long long tiles_both = ((long long)Nc * B + 255) / 256 + ((long long)S * B + 255) / 256;
         bk2 = (c->aux2_stream && tiles_both > current_device_cus() / 2) ? c->aux2_stream : nullptr;
@@ -718,7 +702,6 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
     RNERF_TRY(nerfmlp_dgrad_impl(t.packed_bwd, t.packed_c, prec, bwd, t.save_c, t.d_raw, (int64_t)Nc * B, t.dy, !(pre_zeroed && Nf == 0), true, st));
   if (co) {      // forked HERE, not earlier: the NerfMLP dgrad owns every CU whole, the wgrad below leaves room for these waves
     RNERF_TRY(rnerf_fork(stream, aux));
-    if (kTailDelayTicks > 0) hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, (hipStream_t)aux, (long long)kTailDelayTicks);
     RNERF_TRY(rnerf_bkgd_backward_wgrad(t.save_bk, t.dy_bk, (int64_t)B + M, g_b, 1, aux));
   }
   if (next && next->beside_wgrad && Nf == 0) RNERF_TRY(march_next());

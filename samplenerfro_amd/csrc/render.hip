@@ -525,7 +525,7 @@ using namespace rnerf;
 
 // lanes per ray of the compositing kernels (they are bound by the latency of a ray's chain of sample groups, not by throughput): 64 while a
 // ray per wave still fits one wave per SIMD (<= 1024 rays), 16 up to 8192 rays, 4 beyond.  Measured, forward / backward in us incl. launch
-// (tools/r04/composite_time.py): 128 or 512 rays x 192 samples 41 / 69 (4 lanes), 19 / 26 (16), 20 / 14-17 (64); 4096 x 128: 28 / 48, 20 / 22,
+// (round 4): 128 or 512 rays x 192 samples 41 / 69 (4 lanes), 19 / 26 (16), 20 / 14-17 (64); 4096 x 128: 28 / 48, 20 / 22,
 // 63 / 81; 4096 x 192: 48 / 72, 27 / 32, 85 / 112; 32768 x 128: 53 / 85, 92 / 140, 364 / 444.  RNERF_COMPOSITE_LANES=4|16|64 forces one (A/B, tests).
 static int composite_lanes(int32_t B) {
   static const int forced = [] { const char* e = RNERF_ENV("RNERF_COMPOSITE_LANES"); const int v = e ? atoi(e) : 0; return (v == 4 || v == 16 || v == 64) ? v : 0; }();

@@ -36,7 +36,7 @@ def shared_stream(device, role: str) -> "torch.cuda.Stream":
     """ONE side stream per (device, role) for the whole process, whatever the number of models.  HIP streams are multiplexed onto a few
     hardware queues (GPU_MAX_HW_QUEUES, 4 by default), assigned in creation order: a process that gives every model its own march / tail /
     collective streams soon has two streams of ONE model on one queue, and the work they were meant to overlap runs in sequence (measured:
-    a 128-ray train step 1.11 -> 1.46 ms inside the bench, which builds seven models; tools/r04/variant_probe.sh)."""
+    a 128-ray train step 1.11 -> 1.46 ms inside the bench, which builds seven models; profiles/r04/small_batches.txt)."""
     d = torch.device(device)
     if d.index is None:                     # "cuda" and "cuda:<current>" are one device: one key
         d = torch.device("cuda", torch.cuda.current_device())
@@ -313,7 +313,7 @@ class NerfModel:
 
     def tail2_stream(self) -> torch.cuda.Stream:
         """A third stream of the train step (rnerf_train_cfg.aux2_stream): the background MLP's backward of a small hierarchical batch.
-        Opt-in (RNERF_AUX2_STREAM=1, train.train_cfg): a fifth stream beside default / march / tail / comm no longer gets a hardware queue
+        Opt-in (train._AUX2_STREAM, train.train_cfg): a fifth stream beside default / march / tail / comm no longer gets a hardware queue
         of its own under the default GPU_MAX_HW_QUEUES=4."""
         if getattr(self, "_tail2", None) is None:
             self._tail2 = shared_stream(self.device, "tail2")

@@ -244,10 +244,9 @@ def nerfmlp_pack_bwd(params_flat: torch.Tensor, out: Optional[torch.Tensor] = No
 
 def nerfmlp_backward(packed_bwd, packed_fwd, precision: int, save, d_raw: torch.Tensor, rows: int,
                      grads: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, dy: Optional[torch.Tensor] = None,
-                     stages: str = "dw", backward: int = _lib.BWD_F16X2, return_dy: bool = False, between=None) -> torch.Tensor:
+                     stages: str = "dw", backward: int = _lib.BWD_F16X2, return_dy: bool = False) -> torch.Tensor:
     """d_raw [S,B,4] (d loss / d raw) -> flat fp32 gradient of the NerfMLP parameters (595844 floats).  `backward` (_lib.BWD_*) must be
-    the mode the forward saved for and packed_bwd was packed for.  between: optional callable run after the dgrad launch and before the
-    wgrad launch (train_step issues the next step's march there)."""
+    the mode the forward saved for and packed_bwd was packed for."""
     lib = _lib.load()
     dev = d_raw.device
     dy = torch.empty(lib.rnerf_nerfmlp_dy_bytes(rows, int(backward)), dtype=torch.uint8, device=dev) if dy is None else dy
@@ -256,8 +255,6 @@ def nerfmlp_backward(packed_bwd, packed_fwd, precision: int, save, d_raw: torch.
                                       ptr(dy), current_stream()), "rnerf_nerfmlp_dgrad")
     if "w" not in stages:
         return dy
-    if between is not None:
-        between()
     if grads is None:
         grads = torch.empty(_lib.NERFMLP_PARAMS, dtype=torch.float32, device=dev)
     if workspace is None:
@@ -521,7 +518,7 @@ def finalize_pairs(rec: dict) -> dict:
         # order of so3_mlp's weight gradient.  Re-order the compacted list by its (node, ray) key — unique, so the order is a function of the
         # batch alone — and re-point pair_of_node: every kernel downstream sees the same pairs in the same slots on every run.
         # (int32 keys when they fit, sort + index_select instead of argsort + advanced indexing: the same permutation in fewer, shorter
-        #  launches — 319 -> 270 us for 208 k pairs, tools/r05/dbg_sort.py)
+        #  launches — 319 -> 270 us for 208 k pairs, profiles/r05/README.md)
         small = int(N) * int(B) < 2 ** 31
         key = pid[:, 1] * B + pid[:, 0] if small else pid[:, 1].to(torch.int64) * B + pid[:, 0].to(torch.int64)
         perm = torch.sort(key)[1]

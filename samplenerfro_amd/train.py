@@ -33,21 +33,12 @@ from . import _lib, distributed, ops, prng
 from .models import BKGD_MLP_SHAPES, NERF_MLP_SHAPES, SO3_MLP_SHAPES, NerfModel, make_variables
 from .utils import Rays, Stats, learning_rate_decay
 
-# Experiment switches of the step's stream placement: module attributes (tools set them: `train._MARCH_EARLY = True`), never environment reads.
-_MARCH_EARLY = False                    # see train_step (measured slower: off)
-# CUs the training forward leaves to the next step's march (issued at the START of the step, see train_step); 0 = march after the wgrad.
-# Measured slower (6.8 -> 7.0 ms): the march's 256 one-wave workgroups are dispatched over ALL CUs, and every MLP workgroup (a whole CU
-# each) waits for the wave on its CU; confining the march with a CU-masked stream (hipExtStreamCreateWithCUMask) serialised the two
-# streams instead (7.6 ms), and packing it into 16-wave workgroups on 16 / 32 CUs makes it bound by those CUs' gather units (9.7 / 7.5 ms):
-# the march wants one wave on EVERY CU, the MLP kernels want every CU whole.  Off.
-_MARCH_RESERVE = 0
-_AUX_STREAM = True                      # the second stream of rnerf_train_cfg (False: everything on one stream)
+# Switches of the step's stream placement: module attributes, never environment reads.
 _AUX2_STREAM = False                    # a third stream for the background backward of small hierarchical batches (see train_cfg)
 _CORESIDENT_BKGD_WGRAD = False          # the background-MLP weight gradient as a co-resident kernel beside the NerfMLP wgrad (see train_cfg)
 _RANGE_RETRY_LAG = 2                    # range_retry="lag": the count of step k - 2 is read after step k has been queued (train_step)
 _LAG_SLOTS = 8
 _SKIP_NONFINITE_UPDATES = True          # rnerf_adam_cfg.skip_nonfinite: an update with an inf / NaN gradient entry is skipped and counted (train_step)
-_ALL_CHAIN_BESIDE_WGRAD = True          # stage all*: the march's adjoint chain on the side stream beside the NerfMLP wgrad (see train_step)
 
 _N_STATS = 8        # loss, loss_c, loss_bg, loss_bg_smooth, weight_l2, (3 spare)
 
@@ -287,18 +278,17 @@ def train_cfg(model: NerfModel, state: TrainState, flags, annealed: float) -> "_
     fs = frozen_sq_of(state, state.variables)
     c.frozen_sq, c.frozen_count = fs[0], fs[1]
     # the second stream of rnerf_train_cfg: what depends on the parameters only (operand packing, zeroing the gradient buffer, sum theta^2)
-    # runs there beside the head of the step (_AUX_STREAM = False: everything on one stream)
-    if _AUX_STREAM and hasattr(model, "tail_stream"):
-        c.aux_stream = model.tail_stream().cuda_stream
-        # a third stream for the background backward of small hierarchical batches: opt-in.  It pays at 256 rays (1.48 -> 1.39 ms) when it
-        # gets a hardware queue of its own, and costs 30 % when it lands on the queue of the march or of the main stream — which is decided by
-        # how many streams the process has created (GPU_MAX_HW_QUEUES = 4)
-        if hasattr(model, "tail2_stream") and _AUX2_STREAM:
-            c.aux2_stream = model.tail2_stream().cuda_stream
-        # _CORESIDENT_BKGD_WGRAD (experiment, off): the background-MLP weight gradient as a co-resident kernel beside the NerfMLP wgrad.  Measured
-        # neutral at 4096 x 128 (what it saves on the critical path, ~0.12 ms, the wgrad loses to the extra waves: 2.04 -> 2.2-2.4 ms),
-        # +1-2 % at 1024 rays x (64 + 128)
-        c.coresident_bkgd_wgrad = int(_CORESIDENT_BKGD_WGRAD)
+    # runs there beside the head of the step
+    c.aux_stream = model.tail_stream().cuda_stream
+    # a third stream for the background backward of small hierarchical batches: opt-in.  It pays at 256 rays (1.48 -> 1.39 ms) when it
+    # gets a hardware queue of its own, and costs 30 % when it lands on the queue of the march or of the main stream — which is decided by
+    # how many streams the process has created (GPU_MAX_HW_QUEUES = 4)
+    if _AUX2_STREAM:
+        c.aux2_stream = model.tail2_stream().cuda_stream
+    # _CORESIDENT_BKGD_WGRAD (experiment, off): the background-MLP weight gradient as a co-resident kernel beside the NerfMLP wgrad.  Measured
+    # neutral at 4096 x 128 (what it saves on the critical path, ~0.12 ms, the wgrad loses to the extra waves: 2.04 -> 2.2-2.4 ms),
+    # +1-2 % at 1024 rays x (64 + 128)
+    c.coresident_bkgd_wgrad = int(_CORESIDENT_BKGD_WGRAD)
     return c
 
 
@@ -633,15 +623,8 @@ def _train_step_once(model: NerfModel, rng, state: TrainState, batch: Dict[str, 
     if flags.bg_smooth_weight > 0:
         ev = batch["env_rays"].viewdirs
         ctx["env_dirs"] = ev.reshape(-1, 3)
-    hold = {}
-    if _MARCH_RESERVE > 0 and next_rays is not None and not all_stage:
-        # the NEXT step's march, issued now: it runs beside this step's training forward, which leaves it _MARCH_RESERVE CUs (a dependent
-        # gather chain: 64 waves, as fast on a few CUs as on many)
-        hold["path"] = model.prefetch_path(next_rays, sync_inputs=True, reserve_cus=_MARCH_RESERVE)
     ret, _loss_sp = model.apply(variables, key_0, key_1, rays, flags.randomized, annealed, jitter=jitter, u_fine=u_fine, ctx=ctx, path=path,
                              taps=forward_taps, noise_c=noise_c, noise_f=noise_f)
-    if "path" in hold:
-        model.release_reserved_cus()
     B = ctx["B"]
     rgb_f, _, _, trans_f, tb_f = ret[-1]
     rgb_c = ret[0][0] if len(ret) > 1 else None
@@ -670,29 +653,26 @@ def _train_step_once(model: NerfModel, rng, state: TrainState, batch: Dict[str, 
                                                  trans_f, tb_f, sums, mse_scale, flags.bg_weight * bg_on, rgb_padding=model.rgb_padding,
                                                  sigma_bias=model.sigma_bias, white_bkgd=model.white_bkgd, d_bkgd=d_first, accumulate_bkgd=False,
                                                  mask_bbox=ctx.get("mask_bbox"))
-    # The march of the NEXT step (it reads neither the trained parameters nor anything of this step) goes to the side stream after the
-    # wgrad, beside the small kernels of the step's tail (background-MLP backward, loss glue, Adam).  Those are ~0.35 ms against 0.7-0.8 ms
-    # of march, so ~0.4 ms of every step still waits for it (rocprof timeline) — but issuing it between the dgrad and the
-    # wgrad (RNERF_MARCH_BEFORE_WGRAD=1), where it would be hidden entirely, costs the HBM-paced wgrad more than that: 6.81 -> 7.18 ms.
-    def issue_next_march():
-        hold["path"] = model.prefetch_path(next_rays, sync_inputs=True, reserve_cus=0) if next_rays is not None else None
-    early = _MARCH_EARLY and next_rays is not None and "path" not in hold
-    chain_beside = all_stage and _ALL_CHAIN_BESIDE_WGRAD and hasattr(model, "tail_stream")
-    if chain_beside:
+    if all_stage:
         # stage all*: only the dgrad here; the (HBM-paced) wgrad is issued further down, beside the adjoint chain that needs dY but not dW
         dy_c = ops.nerfmlp_backward(_bwd_packed(model, state, "coarse_mlp", bwd), model._packed_weights(variables, "coarse_mlp"), prec, ctx["save_c"],
                                     d_raw_c, Nc * B, backward=bwd, stages="d")
     else:
         _, dy_c = ops.nerfmlp_backward(_bwd_packed(model, state, "coarse_mlp", bwd), model._packed_weights(variables, "coarse_mlp"), prec, ctx["save_c"],
-                                       d_raw_c, Nc * B, grads=state.grad_view("coarse_mlp"), backward=bwd, return_dy=True,
-                                       between=issue_next_march if early else None)
+                                       d_raw_c, Nc * B, grads=state.grad_view("coarse_mlp"), backward=bwd, return_dy=True)
     # jax.lax.pmean of the gradients (train.py:166), first part: the NerfMLP segments are final here, their all-reduce (95 % of the
     # bytes) starts now and runs beside the rest of the step; the background-MLP gradients and the stats follow in a small second one
     n_big = state.segments["bkgd_mlp"][0]
-    pending = None if chain_beside else distributed.allreduce_begin(G[:n_big])
-    if "path" not in hold:
-        issue_next_march()
-    next_path = hold["path"]
+    pending = None if all_stage else distributed.allreduce_begin(G[:n_big])
+    # The march of the NEXT step (it reads neither the trained parameters nor anything of this step) goes to the side stream after the
+    # wgrad, beside the small kernels of the step's tail (background-MLP backward, loss glue, Adam).  Those are ~0.35 ms against 0.7-0.8 ms
+    # of march, so ~0.4 ms of every step still waits for it (rocprof timeline).  Both earlier places were measured slower:
+    # between the dgrad and the wgrad, where it would be hidden entirely, it costs the HBM-paced wgrad more than that (6.81 -> 7.18 ms);
+    # at the start of the step, beside the training forward with some CUs reserved for it (prefetch_path(reserve_cus=)), 6.8 -> 7.0 ms —
+    # the march's one-wave workgroups are dispatched over ALL CUs and every MLP workgroup (a whole CU each) waits for the wave on its CU; a
+    # CU-masked stream (hipExtStreamCreateWithCUMask) serialised the two streams (7.6 ms), 16-wave march workgroups on 16 / 32 CUs are bound
+    # by those CUs' gather units (9.7 / 7.5 ms).  The march wants one wave on EVERY CU, the MLP kernels want every CU whole.
+    next_path = model.prefetch_path(next_rays, sync_inputs=True, reserve_cus=0) if next_rays is not None else None
     bk_flat = variables["flat"]["bkgd_mlp"]
     g_bk = state.grad_view("bkgd_mlp")
     # ---- env-map smoothness (train.py:127-132): its rows went through the background MLP together with the rays' rows
@@ -702,7 +682,7 @@ def _train_step_once(model: NerfModel, rng, state: TrainState, batch: Dict[str, 
         on = 1.0 if annealed > 0 else 0.0
         env_sum = torch.empty(_lib.load().rnerf_env_smooth_sum_floats(int(ps)), dtype=torch.float32, device=pixels.device)
         ops.env_smooth_backward(ctx["rgb_env"], ps, flags.bg_smooth_weight * on, d_all[B:], env_sum)
-    if all_stage and chain_beside:
+    if all_stage:
         _, d_bk_dirs = ops.bkgd_backward(bk_flat, ctx["save_bkgd"], d_all, g_bk, model.rgb_padding, want_d_dirs=True)
         # Two independent consumers of dY from here on: the NerfMLP weight gradient (one big kernel that streams 10.6 GB and leaves the matrix
         # pipe half idle) and the adjoint chain of the march (input gradients, so3 forward / Jacobians, the reverse scan, so3 backward: ~3.9 ms
@@ -717,9 +697,6 @@ def _train_step_once(model: NerfModel, rng, state: TrainState, batch: Dict[str, 
         with torch.cuda.stream(side):
             _all_stage_backward(model, state, variables, ctx, dy_c, d_bk_dirs, bwd, annealed, taps)
         main.wait_stream(side)
-    elif all_stage:
-        _, d_bk_dirs = ops.bkgd_backward(bk_flat, ctx["save_bkgd"], d_all, g_bk, model.rgb_padding, want_d_dirs=True)
-        _all_stage_backward(model, state, variables, ctx, dy_c, d_bk_dirs, bwd, annealed, taps)
     else:
         ops.bkgd_backward(bk_flat, ctx["save_bkgd"], d_all, g_bk, model.rgb_padding)
     # ---- weight_l2 over ALL variables, the frozen path_sampler included (train.py:147-153), and the Stats scalars: they ride in the

@@ -7,7 +7,7 @@ Emulates the operand roundings of the dgrad chain (dX = dY W^T per layer) and of
     fp8lo   f16 main term + both cross terms on block-scaled e4m3 operands (one power-of-two scale per 32 elements of the reduction
             axis): what a "lo planes stored as fp8" backward would compute (1/3 less matrix time, 1/4 less HBM traffic)
 in float64 products / sums (the MFMA's fp32 accumulation is below what is measured), on the network and cotangent recipe of
-tools/r02/bwd_err.py (rows with cotangents orders of magnitude apart), and prints the worst  max|g - g64| / max|g64|  over the 24 tensors.
+round 2's gradient-error script (rows with cotangents orders of magnitude apart), and prints the worst  max|g - g64| / max|g64|  over the 24 tensors.
 
 usage: python tools/fp8_backward_error.py [rows ...]        (default: 581 4096)
 """

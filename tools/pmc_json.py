@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""(round 3: stamps every csrc file and reads the commit from the tracked VERSION file when .git is absent)
-Collapse rocprofv3 --pmc passes into {kernel: {counter: mean per launch, "avg_ns": kernel-trace mean}} JSON, stamped with the repo
-state.  usage: pmc_json.py out.json note *_counter_collection.csv *_kernel_trace.csv"""
+"""Collapse rocprofv3 --pmc passes (tools/pmc.sh) into {kernel: {counter: mean per launch, "avg_ns": kernel-trace mean}} JSON, stamped with
+the sha of every kernel source and of bench.py (bench.py --full nulls the counter fields of a stale stamp) and with the commit (read from
+the tracked VERSION file when .git is absent).  usage: pmc_json.py out.json note *_counter_collection.csv *_kernel_trace.csv"""
 import collections, csv, hashlib, json, os, re, subprocess, sys
 out, note, files = sys.argv[1], sys.argv[2], sys.argv[3:]
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "samplenerfro_amd", "csrc")
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
 dur = collections.defaultdict(list)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Writes VERSION (tracked): the commit the working tree is based on + a hash of the kernel sources.  The GPU box receives a snapshot without
-# .git, so profile stamps (tools/r03/pmc_json.py) read the commit from this file.  Run before `git commit` of a measured state:
+# .git, so profile stamps (tools/pmc_json.py) read the commit from this file.  Run before `git commit` of a measured state:
 #   bash tools/stamp_version.sh && git add VERSION
 cd "$(dirname "$0")/.."
 head=$(git rev-parse --short=12 HEAD 2>/dev/null || echo unknown)

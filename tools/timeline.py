@@ -16,4 +16,4 @@ for s, e, name, q in seg:
     print(f"  +{(s-t0)/1e3:8.1f} us  gap {(s-end)/1e3:7.1f}  dur {(e-s)/1e3:8.1f}  q{q:>3} {nm}")
     busy += e - s
     end = max(end, e)
-print(f"sum of durations {busy/1e3:.1f} us")
+print(f"sum of durations {busy/1e3:.1f} us, idle {(rows[b][0] - t0 - busy)/1e3:.1f} us (negative: kernels overlapped)")
