@@ -542,6 +542,19 @@ int rnerf_graph_destroy(void* graph_exec);
 int rnerf_fork(void* main_stream, void* side_stream);
 int rnerf_join(void* main_stream, void* side_stream);
 
+/* ---- Evaluation: SSIM.  Replaces utils.compute_ssim (rnerf/utils.py:404-471), called at train.py:449 and eval.py:187.
+ * img0, img1: float[n][H][W][C] (channels last; each of the n leading images and each channel is an independent image); map (nullable):
+ * float[n][H-fs+1][W-fs+1][C]; mean (nullable, not both null): float[n], the mean of each image's map.  The Gaussian window
+ * (filter_size fs in [1, 31], filter_sigma > 0) is computed on the host in double by the reference's formula (:435-439) and rounded to
+ * float once; c1 = (k1 max_val)^2, c2 = (k2 max_val)^2.  NaN propagates as in jnp.maximum / minimum / sign: a NaN pixel makes NaN every
+ * map entry whose window covers it (in its channel) and that image's mean.  The mean is a fixed-order fp64 sum of per-tile partials in
+ * `workspace` (rnerf_ssim_workspace_bytes, 8-byte aligned; unused when mean is null): the same inputs give the same bits on every run.
+ * RNERF_ERR_ARG for fs outside [1, 31] or H < fs or W < fs, RNERF_ERR_UNSUPPORTED when (fs - 1) * C is so large that a tile's
+ * input rows do not fit in LDS (C above about 580 at fs 11); the workspace query then returns 0. */
+size_t rnerf_ssim_workspace_bytes(int64_t n, int32_t H, int32_t W, int32_t C, int32_t filter_size);
+int rnerf_ssim(const float* img0, const float* img1, int64_t n, int32_t H, int32_t W, int32_t C, int32_t filter_size, double filter_sigma,
+               double max_val, double k1, double k2, float* map, float* mean, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

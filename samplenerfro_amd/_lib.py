@@ -157,6 +157,9 @@ SIGNATURES = {
     "rnerf_graph_destroy": (C.c_int, [_vp]),
     "rnerf_fork": (C.c_int, [_vp, _vp]),
     "rnerf_join": (C.c_int, [_vp, _vp]),
+    # evaluation (csrc/metrics.hip)
+    "rnerf_ssim_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32, _i32, _i32]),
+    "rnerf_ssim": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

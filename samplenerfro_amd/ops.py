@@ -620,3 +620,42 @@ def integrated_pos_enc(rows_pd: torch.Tensor, rows_dr: torch.Tensor, node_of_sam
     check(lib.rnerf_integrated_pos_enc(ptr(_chk(rows_pd, "rows_pd")), ptr(_chk(rows_dr, "rows_dr")), ptr(node_of_sample), int(S), int(B), ptr(r), float(near),
                                        int(min_deg), int(max_deg), ptr(mean), ptr(cov), ptr(enc), current_stream()), "rnerf_integrated_pos_enc")
     return (enc, mean, cov) if want_gaussians else enc
+
+
+def ssim(img0: torch.Tensor, img1: torch.Tensor, *, max_val: float, filter_size: int = 11, filter_sigma: float = 1.5, k1: float = 0.01,
+         k2: float = 0.03, return_map: bool = False) -> torch.Tensor:
+    """compute_ssim (rnerf/utils.py:404-471) on the device (rnerf_ssim).  img0, img1: float32 device tensors [..., H, W, C].
+    -> the mean SSIM of each image, shape [...] (0-dim for [H, W, C]), or with return_map the map [..., H-fs+1, W-fs+1, C].
+    Issued on the current stream of the images' device; nothing is synchronised."""
+    if tuple(img0.shape) != tuple(img1.shape):
+        raise ValueError(f"ssim: the images differ in shape: {tuple(img0.shape)} vs {tuple(img1.shape)}")
+    if img0.dim() < 3:
+        raise ValueError(f"ssim: need [..., H, W, C] images, got shape {tuple(img0.shape)}")
+    fs = int(filter_size)
+    *lead, H, W, Ch = (int(s) for s in img0.shape)
+    if not 1 <= fs <= 31:
+        raise ValueError(f"ssim: filter_size must be in [1, 31], got {fs}")
+    if H < fs or W < fs:
+        raise ValueError(f"ssim: the images ({H} x {W}) are smaller than the window (filter_size {fs})")
+    if img0.device != img1.device:
+        raise ValueError(f"ssim: the images are on different devices ({img0.device}, {img1.device})")
+    a, b = _chk(img0, "img0"), _chk(img1, "img1")
+    n = 1
+    for s in lead:
+        n *= s
+    dev = a.device
+    if n == 0 or Ch == 0:
+        return torch.empty(tuple(lead) + ((H - fs + 1, W - fs + 1, Ch) if return_map else ()), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        out_map = torch.empty(tuple(lead) + (H - fs + 1, W - fs + 1, Ch), dtype=torch.float32, device=dev) if return_map else None
+        mean, ws = None, None
+        if not return_map:
+            mean = torch.empty(tuple(lead), dtype=torch.float32, device=dev)
+            nb = lib.rnerf_ssim_workspace_bytes(n, H, W, Ch, fs)
+            if nb == 0:
+                check(-1, "rnerf_ssim_workspace_bytes")
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        check(lib.rnerf_ssim(ptr(a), ptr(b), n, H, W, Ch, fs, float(filter_sigma), float(max_val), float(k1), float(k2), ptr(out_map),
+                             ptr(mean), ptr(ws), torch.cuda.current_stream(dev).cuda_stream), "rnerf_ssim")
+    return out_map if return_map else mean

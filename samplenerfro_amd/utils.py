@@ -1,7 +1,7 @@
 """Host-side mirror of the parts of rnerf/utils.py that sit on the boundary of the hot path.
 
-Rays / Stats / namedtuple_map / render_image / compute_psnr / learning_rate_decay / default flags.  Everything else in
-the reference's utils.py (absl flags, gin, SSIM, image IO) is out of scope.
+Rays / Stats / namedtuple_map / render_image / compute_psnr / compute_ssim (on the device) / save_img / learning_rate_decay /
+default flags.  The rest of the reference's utils.py (absl flags, gin, file-system wrappers) is out of scope.
 """
 from __future__ import annotations
 
@@ -68,6 +68,54 @@ def compute_psnr(mse):
     if isinstance(mse, torch.Tensor):
         return -10.0 / math.log(10.0) * torch.log(mse)
     return -10.0 / math.log(10.0) * math.log(mse)
+
+
+def compute_ssim(img0, img1, max_val, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03, return_map=False):
+    """rnerf/utils.py:404-471 on the device (ops.ssim -> rnerf_ssim); the reference's signature and defaults.
+
+    img0, img1: torch tensors or numpy arrays of one shape [..., H, W, C]; a numpy (or CPU) argument is uploaded to the device of the
+    other argument, or to the current device.  Computed in fp32 (the reference with x64 off).  Returns a device tensor: each image's mean
+    SSIM (shape [...], 0-dim for one [H, W, C] image) or, with return_map, the map [..., H-fs+1, W-fs+1, C].  Nothing is synchronised:
+    `float(ssim)` reads the value back when it is wanted.  There is no CPU fallback."""
+    s0, s1 = tuple(np.shape(img0)), tuple(np.shape(img1))
+    if s0 != s1:
+        raise ValueError(f"compute_ssim: the images differ in shape: {s0} vs {s1}")
+    if len(s0) < 3:
+        raise ValueError(f"compute_ssim: need [..., H, W, C] images, got shape {s0}")
+    if not 1 <= int(filter_size) <= 31:
+        raise ValueError(f"compute_ssim: filter_size must be in [1, 31], got {filter_size}")
+    if s0[-3] < filter_size or s0[-2] < filter_size:
+        raise ValueError(f"compute_ssim: the images ({s0[-3]} x {s0[-2]}) are smaller than the window (filter_size {filter_size})")
+
+    def on_device(t):
+        return isinstance(t, torch.Tensor) and t.is_cuda
+    if on_device(img0):
+        dev = img0.device
+    elif on_device(img1):
+        dev = img1.device
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device())
+
+    def as_f32(t):
+        if not isinstance(t, torch.Tensor):
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float32)))
+        return t.to(device=dev, dtype=torch.float32)
+    from . import ops
+    a, b = as_f32(img0), as_f32(img1)
+    return ops.ssim(a, b, max_val=max_val, filter_size=filter_size, filter_sigma=filter_sigma, k1=k1, k2=k2, return_map=return_map)
+
+
+def save_img(img, pth, to8b=True):
+    """rnerf/utils.py:474-488: a PNG of `img` ([H, W] or [H, W, C]); with to8b the values are clipped to [0, 1] and scaled by 255, the
+    cast to uint8 truncating.  Accepts a device tensor (read back here) or a numpy array."""
+    from PIL import Image
+    if isinstance(img, torch.Tensor):
+        img = img.detach().cpu().numpy()
+    with open(pth, "wb") as imgout:
+        if to8b:
+            Image.fromarray(np.array((np.clip(img, 0., 1.) * 255.).astype(np.uint8))).save(imgout, "PNG")
+        else:
+            Image.fromarray(np.array(img)).save(imgout, "PNG")
 
 
 def learning_rate_decay(step, lr_init, lr_final, max_steps, lr_delay_steps=0, lr_delay_mult=1, lr_start_steps=0):
