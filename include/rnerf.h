@@ -29,13 +29,16 @@ extern "C" {
 #endif
 
 /* Version of this header: entry points AND struct layouts.  2 (round 5): rnerf_grid carries `layout` (so every later field of rnerf_model
- * moved), rnerf_train_cfg carries grads_stream / aux2_stream, rnerf_adam_cfg carries use_lr_override (lr_override alone is ignored).  A
+ * moved), rnerf_train_cfg carries grads_stream, rnerf_adam_cfg carries use_lr_override (lr_override alone is ignored).  A
  * consumer compares rnerf_version() with the RNERF_VERSION it was compiled against before the first call (the Python binding does:
  * samplenerfro_amd/_lib.py load()).
  * 3 (round 6): everything that moved after the first version-2 header — rnerf_composite_backward takes `int mask_mode`, rnerf_adam_cfg carries
  * skip_nonfinite, RNERF_ADAM_SCRATCH_FLOATS is 3076 (was 2052), every f16-based packed NerfMLP buffer ends with a bf16x3 range-safe
- * stream (rnerf_nerfmlp_packed_bytes grew) — and this round's additions: enum rnerf_backward gains F16X3_LO8, rnerf_sample_batch. */
-#define RNERF_VERSION 3
+ * stream (rnerf_nerfmlp_packed_bytes grew) — and this round's additions: enum rnerf_backward gains F16X3_LO8, rnerf_sample_batch.
+ * 4: the opt-in schedule fields no caller set are gone.  rnerf_train_cfg ends with aux_stream, grads_stream (nothing in between);
+ * rnerf_prefetch ends with side_stream (the march always forks right before the last NerfMLP wgrad); rnerf_bkgd_backward is the only
+ * background-MLP backward entry point. */
+#define RNERF_VERSION 4
 
 enum rnerf_status {
   RNERF_OK = 0,
@@ -349,7 +352,7 @@ int rnerf_nerfmlp_dgrad(const void* packed_bwd, const void* packed_fwd, int fwd_
 int rnerf_nerfmlp_wgrad(int fwd_precision, int backward, const void* save, const void* dy, int64_t rows, float* grads, void* workspace,
                         void* stream);
 
-/* ---- T1 (backward of P1+N2): the background MLP, exact fp32 on the matrix cores like its forward.
+/* ---- T1 (backward of P1+N2): the background MLP, exact fp32 on the matrix cores (its forward: f16 hi + lo, like the NerfMLP's f16x3).
  * rnerf_bkgd_forward_train = rnerf_bkgd_forward + `save` (rnerf_bkgd_save_bytes(n) bytes).
  * rnerf_bkgd_backward: d_out float[n][3] (d loss / d activated bkgd colour) -> ACCUMULATES into grads
  * float[RNERF_BKGDMLP_PARAMS] (the caller zeroes it once per step: the per-ray bkgd and the env-map patch, train.py:127-130,
@@ -361,12 +364,6 @@ int rnerf_bkgd_forward_train(const float* params, const float* dirs, int32_t dir
                              float* out_rgb, void* save, void* stream);
 int rnerf_bkgd_backward(const float* params, const void* save, const float* d_out, int64_t n, double rgb_padding, void* dy,
                         float* grads, float* d_dirs, void* stream);
-/* The two halves of rnerf_bkgd_backward, for a host that overlaps them with other work: _dgrad fills dy (and d_dirs); _wgrad accumulates
- * grads from (save, dy).  coresident != 0 selects a wgrad kernel of at most 80 registers per lane and no LDS, which fits beside the
- * NerfMLP wgrad's waves on every CU (rnerf_train_cfg.coresident_bkgd_wgrad). */
-int rnerf_bkgd_backward_dgrad(const float* params, const void* save, const float* d_out, int64_t n, double rgb_padding, void* dy, float* d_dirs,
-                              void* stream);
-int rnerf_bkgd_backward_wgrad(const void* save, void* dy, int64_t n, float* grads, int coresident, void* stream);
 
 /* ---- training of stage "all*" — jax.value_and_grad (train.py:164) through the N-step eikonal recurrence
  * (rnerf/eikonal_utils.py:29-49,100-124) and through so3_mlp + the Rodrigues rotation (rnerf/ior_utils.py:269-312), with path_sampler
@@ -480,18 +477,14 @@ typedef struct rnerf_train_cfg {
   void* aux_stream;            /* nullable: a second stream.  Everything of a step that depends on the parameters only — packing the operand streams of
                                   both directions, zeroing the gradient buffer, sum theta^2 — runs there beside the key kernels, the march and the
                                   background-MLP forward, and is joined inside the call before the first NerfMLP kernel */
-  int32_t coresident_bkgd_wgrad;  /* experiment (needs aux_stream): the background MLP's weight gradient as a co-resident kernel beside the NerfMLP wgrad */
   void* grads_stream;          /* nullable: a stream the call orders behind the LAST NerfMLP wgrad (rnerf_fork at that point).  grads[0 .. NerfMLP
                                   segments) are final there: a caller with more than one rank starts their all-reduce (jax.lax.pmean, train.py:166 —
                                   95 % of the bytes) on this stream as soon as the call returns, beside the background-MLP backward and the loss tail
                                   still queued on `stream`, and joins before rnerf_adam_update */
-  void* aux2_stream;           /* nullable (needs aux_stream): a third stream for hierarchical models at small batches, where the two levels' backward
-                                  passes run side by side: the background MLP's backward (it needs d loss / d background only, final once both
-                                  compositing backwards have run) goes there, beside both NerfMLP chains instead of in front of the coarse one */
 } rnerf_train_cfg;
 /* The march of the NEXT batch (it reads neither the parameters nor anything of this step): when `next` is given, its rays are marched on
- * next->side_stream, forked from `stream` right behind the last NerfMLP wgrad, so that the latency-bound march runs beside the small
- * kernels of the step's tail.  The caller joins (rnerf_join(stream, side_stream)) before it reads next->path_* — inside a captured graph:
+ * next->side_stream, forked from `stream` right before the last NerfMLP wgrad, so that the latency-bound march runs as co-resident waves
+ * beside that HBM-paced kernel.  The caller joins (rnerf_join(stream, side_stream)) before it reads next->path_* — inside a captured graph:
  * before rnerf_graph_end. */
 typedef struct rnerf_prefetch {
   const float* origins;        /* float[B][3] of the next batch */
@@ -499,7 +492,6 @@ typedef struct rnerf_prefetch {
   float* path_pd;              /* float4[N][B] each: where the next batch's path record goes */
   float* path_dr;
   void* side_stream;
-  int32_t beside_wgrad;        /* != 0: fork BEFORE the last wgrad instead of behind it (the march co-resident with the wgrad's waves) */
 } rnerf_prefetch;
 size_t rnerf_train_workspace_bytes(const rnerf_model* m, const rnerf_train_cfg* c, int32_t B);
 int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_train_cfg* c, const float* theta, const float* origins, const float* viewdirs,

@@ -23,7 +23,7 @@ BWD_F16X3_LO8 = 4        # f16x3 with the lo planes of the saved operands / grad
 BACKWARDS = {"f16x3": BWD_F16X3, "f16x3lo8": BWD_F16X3_LO8, "f16": BWD_F16, "bf16": BWD_BF16, "f32": BWD_F16X3, "tf32": BWD_F16}
 BACKWARD_NAMES = {BWD_F16X3: "f16x3", BWD_F16X3_LO8: "f16x3lo8", BWD_F16: "f16", BWD_BF16: "bf16"}
 TWO_PLANE_BACKWARDS = (BWD_F16X3, BWD_F16X3_LO8)
-ABI_VERSION = 3          # == RNERF_VERSION of include/rnerf.h; load() refuses a library that answers anything else
+ABI_VERSION = 4          # == RNERF_VERSION of include/rnerf.h; load() refuses a library that answers anything else
 NERFMLP_PARAMS = 595844
 BKGDMLP_PARAMS = 56963
 SO3MLP_PARAMS = 65411
@@ -62,8 +62,7 @@ class TrainCfg(C.Structure):
     """rnerf_train_cfg: the loss terms of train_step.loss_fn that the shipped configs switch on (train.py:75-162)."""
     _fields_ = [("backward", C.c_int32), ("randomized", C.c_int32), ("use_random_choice", C.c_int32), ("bg_patch_size", C.c_int32),
                 ("bg_weight", C.c_double), ("bg_smooth_weight", C.c_double), ("annealed_alpha", C.c_double), ("frozen_sq", C.c_double),
-                ("frozen_count", C.c_int64), ("aux_stream", C.c_void_p), ("coresident_bkgd_wgrad", C.c_int32), ("grads_stream", C.c_void_p),
-                ("aux2_stream", C.c_void_p)]
+                ("frozen_count", C.c_int64), ("aux_stream", C.c_void_p), ("grads_stream", C.c_void_p)]
 
 
 class AdamCfg(C.Structure):
@@ -75,9 +74,8 @@ class AdamCfg(C.Structure):
 
 
 class Prefetch(C.Structure):
-    """rnerf_prefetch: the next batch's march on a side stream, forked behind the last wgrad of rnerf_train_forward_backward."""
-    _fields_ = [("origins", C.c_void_p), ("viewdirs", C.c_void_p), ("path_pd", C.c_void_p), ("path_dr", C.c_void_p), ("side_stream", C.c_void_p),
-                ("beside_wgrad", C.c_int32)]
+    """rnerf_prefetch: the next batch's march on a side stream, forked right before the last wgrad of rnerf_train_forward_backward."""
+    _fields_ = [("origins", C.c_void_p), ("viewdirs", C.c_void_p), ("path_pd", C.c_void_p), ("path_dr", C.c_void_p), ("side_stream", C.c_void_p)]
 
 
 LEVEL_FLOATS = 9
@@ -128,8 +126,6 @@ SIGNATURES = {
     "rnerf_bkgd_dy_bytes": (C.c_size_t, [_i64]),
     "rnerf_bkgd_forward_train": (C.c_int, [_vp, _vp, _i32, _i64, _dbl, _vp, _vp, _vp]),
     "rnerf_bkgd_backward": (C.c_int, [_vp, _vp, _vp, _i64, _dbl, _vp, _vp, _vp, _vp]),
-    "rnerf_bkgd_backward_dgrad": (C.c_int, [_vp, _vp, _vp, _i64, _dbl, _vp, _vp, _vp]),
-    "rnerf_bkgd_backward_wgrad": (C.c_int, [_vp, _vp, _i64, _vp, C.c_int, _vp]),
     "rnerf_theta_sumsq": (C.c_int, [_vp, _i64, _vp, _vp]),
     "rnerf_march_all_train": (C.c_int, [_vp, _GP, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rnerf_so3_packed_bytes": (C.c_size_t, []),

@@ -1,6 +1,6 @@
 // The background MLP on the f16 matrix cores (round 4): forward (inference / training) of MLP(128, 4, skip 2, out 3) on pos_enc(dir, 0, 4)
 // + the rgb activation.  Reference: rnerf/models.py:181-191 (forward_envmap), :303, :336-337; rnerf/model_utils.py:93-140 (MLP), :187-214.
-// The exact-fp32 kernels of the same network (the arbiter of this file: RNERF_BKGD_EXACT=1) and the backward kernels live in csrc/mlp.hip.
+// The backward kernels of the same network (exact fp32 MFMA) live in csrc/mlp.hip.
 #include "mfma_ops.h"
 #include "bkgd_layout.h"
 #include "so3_layout.h"
@@ -8,14 +8,13 @@
 namespace rnerf {
 
 // ---- the background MLP on the f16 matrix cores (round 4) ---------------------------------------------------------------------------
-// The exact-fp32 chain above (v_mfma_f32_32x32x2_f32: 64 cycles per K = 2 step, ~900 per 32 rows) is bound by the latency of its one wave
+// An exact-fp32 chain (v_mfma_f32_32x32x2_f32: 64 cycles per K = 2 step, ~900 per 32 rows) is bound by the latency of its one wave
 // per row block: 64 us for the 20 480 rows of a bench step, at the head of every step.  The same network with the f16 hi + lo split of the
 // NerfMLP engine (3 x v_mfma_f32_32x32x16_f16 per tile: 340 MFMAs of 32 cycles per 32 rows, fp32 accumulate, weights x 2^8 so that the lo
 // parts stay normal; error class 2^-22 like f16x3) — the weights are converted on the fly from the flat fp32 buffer (every wave reads the
 // 57 k parameters through L1 / L2: no packed stream, no change to the C ABI), the transposed chain keeps the activations in registers
 // (accumulator layout = next layer's B operand: prev_feature / view_feature slot maps as in the NerfMLP engine).  Saved tensors of the
-// training forward: the same fp32 layout as bkgd_fwd_kernel (the backward kernels do not care which arithmetic produced X_k).
-// RNERF_BKGD_EXACT=1 selects the exact-fp32 kernels (they stay the arbiter of this one: tests/test_gpu_parity.py).
+// training forward: fp32, in the layout the backward kernels read (bkgd_layout.h).  Held to the numpy oracle: tests/test_gpu_parity.py.
 // (A three-instruction split — v_cvt_pk_f16_f32, then v_fma_mixlo_f16 / v_fma_mixhi_f16 subtracting the f16 half straight from the packed
 //  word — gives the same bits alone (profiles/r04/bkgd16.txt) but NaNs in this kernel: inline asm hides the partial-register
 //  writes from the compiler's hazard recogniser.  It bought 1 us of 21: the kernel is bound by latency, not by its conversions.)
@@ -135,7 +134,7 @@ __global__ void __launch_bounds__(64) bkgd16_fwd_kernel(const float* __restrict_
   const bool ok = row < n;
   if (!ok) row = n - 1;
   const float v0 = dirs[row * dir_stride], v1 = dirs[row * dir_stride + 1], v2 = dirs[row * dir_stride + 2];
-  float enc[14];                                     // as bkgd_fwd_kernel: the same values in the same slots
+  float enc[14];                                     // pos_enc(dir, 0, 4) (rnerf/model_utils.py:187-214) in the K=2 slot order of dir_feature
   const float phase = h ? 1.5707963705062866f : 0.0f;
 #pragma unroll
   for (int q = 0; q < 12; ++q) {
@@ -223,8 +222,8 @@ int launch_bkgd16_fwd(bool train, const float* params, const float* dirs, int di
 // ---- so3_mlp: the training forward of stage "all*" on the same arithmetic --------------------------------------------------------------
 // MLP(128, 4, skip 2, out 3) on the 60 windowed encoding features (rnerf/ior_utils.py:148-152, rnerf/model_utils.py:236-245): lane half h
 // holds feature 2 p + h in enc[p] (so3_encode), i.e. four k-steps of 8 slots with p = 8 s + j, slot p = 30 free for the bias.  The prev-layer
-// blocks are the background MLP's (same [128][128] kernels, same slot map).  Saved tensors: the layout of so3_fwd_train_kernel (the exact-fp32
-// kernel of csrc/ior_train_kernels.inc, which stays selectable with RNERF_BKGD_EXACT=1 and is what the backward kernels were written against).
+// blocks are the background MLP's (same [128][128] kernels, same slot map).  Saved tensors: the fp32 layout of csrc/so3_layout.h, which the backward
+// kernels of csrc/ior_train_kernels.inc read.
 template <bool FIRST>
 __device__ __forceinline__ void so3_16_enc_layer(f32x16 (&acc)[4], const float (&enc)[30], const float* __restrict__ pe, const Bkgd16Lane& L, int koff, int boff) {
   bkgd16_layer<4, FIRST>(acc,

@@ -9,8 +9,9 @@
 
 // Experiment / test switches.  The product library reads NO environment variable (include/rnerf.h: no global state, nothing a stray
 // RNERF_* variable on a bench box could change): RNERF_ENV folds to a null pointer and every switch to its default at compile time.
-// librnerf_experiments.so (build.py, -DRNERF_EXPERIMENTS) is the same source with the switches live, for tools/ and for the tests that
-// compare two launch shapes bit for bit (tests/test_gpu_half_tiles.py, tests/test_gpu_composite_lanes.py).
+// librnerf_experiments.so (build.py, -DRNERF_EXPERIMENTS) is the same source with the switches live: RNERF_FWD_HALF_TILES,
+// RNERF_DGRAD_HALF_TILES and RNERF_COMPOSITE_LANES for the tests that compare two launch shapes bit for bit (tests/test_gpu_half_tiles.py,
+// tests/test_gpu_composite_lanes.py), RNERF_WGRAD_TRACE as a profiling aid.
 #ifdef RNERF_EXPERIMENTS
 #include <stdlib.h>
 #define RNERF_ENV(name) getenv(name)

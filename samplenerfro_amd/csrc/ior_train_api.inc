@@ -31,11 +31,7 @@ extern "C" int rnerf_so3_forward_train(const float* so3_params, const float* win
   RNERF_CHECK_ARG(n >= 1, "rnerf_so3_forward_train: n must be >= 1");
   So3Window w;
   for (int i = 0; i < 10; ++i) w.w[i] = window10[i];
-  if (!bkgd_exact()) return launch_so3_16_fwd_train(so3_params, w, pts4, (long long)n, (float*)save, (hipStream_t)stream);      // f16 hi + lo MFMAs (csrc/bkgd16.hip)
-  hipLaunchKernelGGL(so3_fwd_train_kernel, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, (hipStream_t)stream, so3_params, w, (const float4*)pts4,
-                     (long long)n, (float*)save);
-  RNERF_CHECK_LAUNCH();
-  return RNERF_OK;
+  return launch_so3_16_fwd_train(so3_params, w, pts4, (long long)n, (float*)save, (hipStream_t)stream);      // f16 hi + lo MFMAs (csrc/bkgd16.hip)
 }
 
 extern "C" int rnerf_so3_backward(const float* so3_params, const float* window10, const float* pts4, const void* save, int64_t n_save,

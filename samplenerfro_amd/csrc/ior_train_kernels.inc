@@ -16,72 +16,8 @@
 // a_p / a_d come from nerfmlp_input_grad_kernel (d loss / d position and direction of every coarse sample: through the position /
 // view encodings of Dense_0, the skip concat of Dense_5 and the view layer Dense_10) and from the background MLP's input gradient.
 
-// ---- so3 MLP, exact fp32 on v_mfma_f32_32x32x2_f32 like the background MLP ----------------------------------------------------------
-// (layouts + so3_encode: csrc/so3_layout.h, shared with the f16 hi + lo training forward of csrc/bkgd16.hip)
-__global__ void __launch_bounds__(64) so3_fwd_train_kernel(const float* __restrict__ params, So3Window win, const float4* __restrict__ pts, long long n,
-                                                           float* __restrict__ save) {
-  const int lane = threadIdx.x & 63, m = lane & 31, h = lane >> 5;
-  long long row = (long long)blockIdx.x * 32 + m;
-  const bool ok = row < n;
-  if (!ok) row = n - 1;
-  const float4 pt = pts[row];
-  float enc[30];
-  so3_encode(pt.x, pt.y, pt.z, win, h, enc);
-  if (ok) {
-#pragma unroll
-    for (int p = 0; p < 30; ++p) save[(size_t)row * 60 + 2 * p + h] = enc[p];
-  }
-  auto save_x = [&](int k, const f32x16 (&xx)[4]) {     // X_k[row][f], f = 32t + 8g + 4h + i
-    so3_store_mask(save, n, row, k, xx, h, ok);         // + the 128 sign bits the dgrad reads (every lane takes part in the half-lane exchange)
-    if (ok) {
-      float* dst = save + (size_t)n * 60 + (size_t)(k - 1) * n * 128 + (size_t)row * 128;
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *(float4*)(dst + 32 * t + 8 * g + 4 * h) = make_float4(xx[t][4 * g], xx[t][4 * g + 1], xx[t][4 * g + 2], xx[t][4 * g + 3]);
-    }
-  };
-  f32x16 acc[4], x[4];
-  small_init_bias(acc, params + so3_boff(0), h);
-  so3_enc_layer(acc, enc, params + so3_koff(0), m, h);
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) x[t][r] = fmaxf(acc[t][r], 0.f);
-  save_x(1, x);
-#pragma unroll 1
-  for (int l = 1; l <= 2; ++l) {
-    small_init_bias(acc, params + (l == 1 ? so3_boff(1) : so3_boff(2)), h);
-    small_prev_layer(acc, x, params + (l == 1 ? so3_koff(1) : so3_koff(2)), m, h);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) x[t][r] = fmaxf(acc[t][r], 0.f);
-    save_x(l + 1, x);
-  }
-  small_init_bias(acc, params + so3_boff(3), h);
-  small_prev_layer(acc, x, params + so3_koff(3), m, h);
-  so3_enc_layer(acc, enc, params + so3_koff(3) + 128 * 128, m, h);
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) x[t][r] = fmaxf(acc[t][r], 0.f);
-  save_x(4, x);
-  float o[3] = {0.f, 0.f, 0.f};
-  const float* __restrict__ k4 = params + so3_koff(4);
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int f = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
-      o[0] = fmaf(x[t][r], k4[f * 3 + 0], o[0]); o[1] = fmaf(x[t][r], k4[f * 3 + 1], o[1]); o[2] = fmaf(x[t][r], k4[f * 3 + 2], o[2]);
-    }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) o[c] = o[c] + __shfl_xor(o[c], 32) + params[so3_boff(4) + c];
-  if (ok && h == 0) *(float4*)(save + (size_t)n * (60 + 4 * 128) + (size_t)row * 4) = make_float4(o[0], o[1], o[2], 0.f);
-}
-
+// ---- so3 MLP backward, exact fp32 on v_mfma_f32_32x32x2_f32 like the background MLP's -------------------------------------------------
+// (the training forward is the f16 hi + lo one of csrc/bkgd16.hip; layouts + so3_encode: csrc/so3_layout.h)
 // dgrad chain of the so3 MLP + the gradient w.r.t. the input point.  Row `row` of the batch uses the saved activations of row
 // `row % n_save` (the Jacobian pass runs the three unit cotangents of every point as one batch of 3 n_save rows).
 __global__ void __launch_bounds__(64) so3_dgrad_kernel(const float* __restrict__ params, So3Window win, const float4* __restrict__ pts,

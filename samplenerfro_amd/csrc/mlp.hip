@@ -2225,13 +2225,14 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// N2: the 4x128 background MLP (rnerf/models.py:116-118) in exact fp32 on v_mfma_f32_32x32x2_f32.
-// One wave = 32 rays; weights are read straight from the flat fp32 buffer (kernel[in][out], coalesced along out).
+// N2: the 4x128 background MLP (rnerf/models.py:116-118) and so3_mlp in exact fp32 on v_mfma_f32_32x32x2_f32: the building blocks of
+// so3_eval and of the backward kernels below (the background MLP's forward runs on the f16 matrix cores: csrc/bkgd16.hip).
+// One wave = 32 rows; weights are read straight from the flat fp32 buffer (kernel[in][out], coalesced along out).
 // ------------------------------------------------------------------------------------------------------------------
 // acc[t] += W(step, t) * x(step) over NSTEP K=2 steps of v_mfma_f32_32x32x2_f32 for NT n-tiles, with the per-lane weight dwords fetched one
 // BATCH (4 steps) ahead of the MFMAs that consume them.  Left to itself hipcc emits load -> s_waitcnt vmcnt(0) -> MFMA for every single
 // product, re-using one register: a full L2 round trip (~650 cycles) per 64-cycle MFMA — the small-MLP kernels ran at a tenth of the
-// matrix rate (so3_fwd_train_kernel 1.77 ms for 208 k rows).  wload(step, t) must be a pure load of a lane-dependent address, x(step) a
+// matrix rate (the so3 training forward: 1.77 ms for 208 k rows).  wload(step, t) must be a pure load of a lane-dependent address, x(step) a
 // register operand; both are called with constants after unrolling.  Same products in the same order: same bits.
 template <int NSTEP, int NT, typename WF, typename XF>
 __device__ __forceinline__ void mfma_f32_stream(f32x16* acc, WF wload, XF xop) {
@@ -2302,108 +2303,6 @@ __device__ __forceinline__ void small_prev_layer(f32x16 (&acc)[4], const f32x16 
   mfma_f32_stream<64, 4>(acc, [&](int st, int t) { return kl[(32 * (st >> 4) + (st & 3) + 8 * ((st & 15) >> 2)) * 128 + 32 * t]; },
                          [&](int st) { return x[st >> 4][st & 15]; });
 }
-
-__device__ __forceinline__ void small_dir_layer(f32x16 (&acc)[4], const float (&enc)[14], const float* __restrict__ kern, int m, int h) {
-  mfma_f32_stream<14, 4>(acc, [&](int q, int t) {
-    const int f = h ? dir_feature(q, 1) : dir_feature(q, 0);
-    const float w = kern[(f < 0 ? 0 : f) * 128 + 32 * t + m];
-    return f < 0 ? 0.f : w;
-  }, [&](int q) { return enc[q]; });
-}
-
-template <bool TRAIN>
-__global__ void __launch_bounds__(64) bkgd_fwd_kernel(const float* __restrict__ params, const float* __restrict__ dirs, int dir_stride,
-                                                      long long n, float pad_scale, float pad, float* __restrict__ out_rgb,
-                                                      float* __restrict__ save) {
-  const int lane = threadIdx.x & 63, m = lane & 31, h = lane >> 5;
-  long long row = (long long)blockIdx.x * 32 + m;
-  const bool ok = row < n;
-  if (!ok) row = n - 1;
-  const float v0 = dirs[row * dir_stride], v1 = dirs[row * dir_stride + 1], v2 = dirs[row * dir_stride + 2];
-  // pos_enc(dir, 0, 4) (rnerf/model_utils.py:187-214) in the K=2 slot order of dir_feature
-  float enc[14];
-  const float phase = h ? 1.5707963705062866f : 0.0f;
-#pragma unroll
-  for (int q = 0; q < 12; ++q) {
-    const int d = q / 3, c = q % 3;
-    const float x = c == 0 ? v0 : (c == 1 ? v1 : v2);
-    enc[q] = sinf(fadd(fmul(x, (float)(1 << d)), phase));
-  }
-  enc[12] = h ? v2 : v0;
-  enc[13] = h ? 0.f : v1;
-  auto save_x = [&](int k, const f32x16 (&xx)[4]) {     // X_k[row][f], f = 32t + 8g + 4h + i
-    if constexpr (TRAIN) {
-      if (ok) {
-        float* dst = save + (size_t)n * 28 + (size_t)(k - 1) * n * 128 + (size_t)row * 128;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            *(float4*)(dst + 32 * t + 8 * g + 4 * h) = make_float4(xx[t][4 * g], xx[t][4 * g + 1], xx[t][4 * g + 2], xx[t][4 * g + 3]);
-      }
-    }
-  };
-  if constexpr (TRAIN) {
-    if (ok) {
-#pragma unroll
-      for (int q = 0; q < 14; ++q) { const int f = h ? dir_feature(q, 1) : dir_feature(q, 0); if (f >= 0) save[(size_t)row * 28 + f] = enc[q]; }
-      if (h == 1) save[(size_t)row * 28 + 27] = 0.f;
-    }
-  }
-
-  f32x16 acc[4], x[4];
-  // Dense_0: 27 -> 128, ReLU
-  small_init_bias(acc, params + bkgd_boff(0), h);
-  small_dir_layer(acc, enc, params + bkgd_koff(0), m, h);
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) x[t][r] = fmaxf(acc[t][r], 0.f);
-  save_x(1, x);
-  // Dense_1, Dense_2: 128 -> 128, ReLU
-#pragma unroll 1
-  for (int l = 1; l <= 2; ++l) {
-    small_init_bias(acc, params + (l == 1 ? bkgd_boff(1) : bkgd_boff(2)), h);
-    small_prev_layer(acc, x, params + (l == 1 ? bkgd_koff(1) : bkgd_koff(2)), m, h);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) x[t][r] = fmaxf(acc[t][r], 0.f);
-    save_x(l + 1, x);
-  }
-  // Dense_3: [x(128), inputs(27)] -> 128, ReLU  (skip concat after i == 2, rnerf/model_utils.py:131-132)
-  small_init_bias(acc, params + bkgd_boff(3), h);
-  small_prev_layer(acc, x, params + bkgd_koff(3), m, h);
-  small_dir_layer(acc, enc, params + bkgd_koff(3) + 128 * 128, m, h);
-  // Dense_4: 128 -> 3 on the VALU, then sigmoid*(1+2p)-p (rnerf/models.py:336-337)
-  if constexpr (TRAIN) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) x[t][r] = fmaxf(acc[t][r], 0.f);
-    save_x(4, x);
-  }
-  float o[3] = {0.f, 0.f, 0.f};
-  const float* __restrict__ k4 = params + bkgd_koff(4);
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float v = fmaxf(acc[t][r], 0.f);
-      const int f = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
-      o[0] = fmaf(v, k4[f * 3 + 0], o[0]); o[1] = fmaf(v, k4[f * 3 + 1], o[1]); o[2] = fmaf(v, k4[f * 3 + 2], o[2]);
-    }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    o[c] = o[c] + __shfl_xor(o[c], 32) + params[bkgd_boff(4) + c];
-    o[c] = fsub(fmul(fdiv(1.0f, fadd(1.0f, expf(-o[c]))), pad_scale), pad);
-  }
-  if (ok && h == 0) {
-    out_rgb[3 * row] = o[0]; out_rgb[3 * row + 1] = o[1]; out_rgb[3 * row + 2] = o[2];
-    if constexpr (TRAIN) { float* so = save + (size_t)n * (28 + 4 * 128) + (size_t)row * 3; so[0] = o[0]; so[1] = o[1]; so[2] = o[2]; }
-  }
-}
-
 
 // ------------------------------------------------------------------------------------------------------------------
 // G4 / P2 / E1 (stage "all"): so3_mlp = MLP(128, 4, skip 2, out 3) on annealed_pos_enc(x) (rnerf/ior_utils.py:148-152, :283;
@@ -3077,66 +2976,6 @@ __global__ void __launch_bounds__(256) bkgd_wgrad_kernel(const float* __restrict
   }
 }
 
-// The same wgrad as a kernel that can be CO-RESIDENT with the NerfMLP wgrad (which keeps 64-80 registers per SIMD free and nearly all
-// of the LDS for itself): one wave per (256-row chunk, unit, pair of n-tiles), at most 80 registers, no LDS — the partial of a chunk is
-// written by the wave that computed it.  It is slower than bkgd_wgrad_kernel when it runs alone (no unrolling headroom), which does
-// not matter where it is used: on a side stream beside the 2 ms NerfMLP wgrad, off the step's critical path (csrc/pipeline.hip).
-template <int KIND>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(40)))
-bkgd_wgrad_co_kernel(const float* __restrict__ save, const float* __restrict__ dy, long long n, float* __restrict__ partial) {
-  const BkgdUnit u = KIND == 0 ? kBkgdUnits[blockIdx.y] : kSo3Units[blockIdx.y];
-  const int lane = threadIdx.x & 63, m = lane & 31, h = lane >> 5;
-  const int NT = (u.nout + 31) / 32;
-  const int np = blockIdx.z;                          // n-tiles {2 np, 2 np + 1} = columns {4 m + 2 np, 4 m + 2 np + 1}
-  if (NT == 1 && np != 0) return;
-  const float* __restrict__ X = u.xk == 0 ? save : save + (size_t)n * SmallNet<KIND>::ENC_LD + (size_t)(u.xk - 1) * n * 128;
-  const float* __restrict__ dY = dy + (size_t)u.dk * n * 128;
-  const int k = 32 * u.kt + m;
-  const int kc = k < u.kin ? k : u.kin - 1;
-  const bool bias = u.boff >= 0;
-  const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  f32x16 acc0 = zero, acc1 = zero;
-  float bs0 = 0.f, bs1 = 0.f;
-  const long long r0 = (long long)blockIdx.x * 256;
-#pragma unroll 4
-  for (int i = 0; i < 128; ++i) {
-    const long long rr = r0 + 2 * i + h;
-    const bool ok = rr < n;
-    const size_t rc = (size_t)(ok ? rr : n - 1);
-    const float av = X[rc * u.ldx + kc];
-    const float a = (ok && k < u.kin) ? av : 0.f;
-    if (NT == 4) {
-      const float2 bv = *(const float2*)(dY + rc * 128 + 4 * m + 2 * np);
-      const float b0 = ok ? bv.x : 0.f, b1 = ok ? bv.y : 0.f;
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc1, 0, 0, 0);
-      bs0 += b0; bs1 += b1;
-    } else {
-      const float bv = dY[rc * u.ldy + (m < u.nout ? m : u.nout - 1)];
-      const float b0 = (ok && m < u.nout) ? bv : 0.f;
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc0, 0, 0, 0);
-      bs0 += b0;
-    }
-  }
-  float* pg = partial + (size_t)blockIdx.x * SmallNet<KIND>::NPARAMS;
-  bs0 += __shfl_xor(bs0, 32); bs1 += __shfl_xor(bs1, 32);
-  const int nn0 = NT == 4 ? 4 * m + 2 * np : m;
-  if (nn0 < u.nout) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int ki = 32 * u.kt + (r & 3) + 8 * (r >> 2) + 4 * h;
-      if (ki < u.kin) {
-        pg[u.goff + ki * u.out_dim + nn0] = acc0[r];
-        if (NT == 4) pg[u.goff + ki * u.out_dim + nn0 + 1] = acc1[r];
-      }
-    }
-    if (bias && h == 0) {
-      pg[u.boff + nn0] = bs0;
-      if (NT == 4) pg[u.boff + nn0 + 1] = bs1;
-    }
-  }
-}
-
 template <int NPARAMS>
 __global__ void __launch_bounds__(256) bkgd_wgrad_reduce_kernel(const float* __restrict__ partial, int chunks, float* __restrict__ grads) {
   const int e = blockIdx.x * 256 + threadIdx.x;
@@ -3661,24 +3500,12 @@ extern "C" int rnerf_nerfmlp_wgrad(int fwd_precision, int backward, const void* 
   return RNERF_OK;
 }
 
-// RNERF_BKGD_EXACT=1: the exact-fp32 background-MLP kernels (v_mfma_f32_32x32x2_f32) instead of the f16 hi + lo ones (read once)
-static bool bkgd_exact() {
-  static const bool v = [] { const char* e = RNERF_ENV("RNERF_BKGD_EXACT"); return e && e[0] == '1'; }();
-  return v;
-}
-
 extern "C" int rnerf_bkgd_forward(const float* params, const float* dirs, int32_t dir_stride, int64_t n, double rgb_padding,
                                   float* out_rgb, void* stream) {
   RNERF_CHECK_ARG(params && dirs && out_rgb, "rnerf_bkgd_forward: null pointer");
   RNERF_CHECK_ARG(dir_stride >= 3, "rnerf_bkgd_forward: dir_stride must be >= 3");
   RNERF_CHECK_ARG(n >= 1, "rnerf_bkgd_forward: n must be >= 1");
-  if (bkgd_exact())
-    hipLaunchKernelGGL(bkgd_fwd_kernel<false>, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, (hipStream_t)stream, params, dirs, dir_stride,
-                       (long long)n, (float)(1 + 2 * rgb_padding), (float)rgb_padding, out_rgb, (float*)nullptr);
-  else
-    return launch_bkgd16_fwd(false, params, dirs, dir_stride, (long long)n, (float)(1 + 2 * rgb_padding), (float)rgb_padding, out_rgb, nullptr, (hipStream_t)stream);
-  RNERF_CHECK_LAUNCH();
-  return RNERF_OK;
+  return launch_bkgd16_fwd(false, params, dirs, dir_stride, (long long)n, (float)(1 + 2 * rgb_padding), (float)rgb_padding, out_rgb, nullptr, (hipStream_t)stream);
 }
 
 extern "C" size_t rnerf_bkgd_save_bytes(int64_t n) { return bkgd_save_floats(n) * sizeof(float); }
@@ -3688,49 +3515,26 @@ extern "C" int rnerf_bkgd_forward_train(const float* params, const float* dirs, 
                                         float* out_rgb, void* save, void* stream) {
   RNERF_CHECK_ARG(params && dirs && out_rgb && save, "rnerf_bkgd_forward_train: null pointer");
   RNERF_CHECK_ARG(dir_stride >= 3 && n >= 1, "rnerf_bkgd_forward_train: need dir_stride >= 3 and n >= 1");
-  if (bkgd_exact())
-    hipLaunchKernelGGL(bkgd_fwd_kernel<true>, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, (hipStream_t)stream, params, dirs, dir_stride,
-                       (long long)n, (float)(1 + 2 * rgb_padding), (float)rgb_padding, out_rgb, (float*)save);
-  else
-    return launch_bkgd16_fwd(true, params, dirs, dir_stride, (long long)n, (float)(1 + 2 * rgb_padding), (float)rgb_padding, out_rgb, (float*)save, (hipStream_t)stream);
-  RNERF_CHECK_LAUNCH();
-  return RNERF_OK;
-}
-
-extern "C" int rnerf_bkgd_backward_dgrad(const float* params, const void* save, const float* d_out, int64_t n, double rgb_padding, void* dy,
-                                         float* d_dirs, void* stream) {
-  RNERF_CHECK_ARG(params && save && d_out && dy, "rnerf_bkgd_backward_dgrad: null pointer");
-  RNERF_CHECK_ARG(n >= 1, "rnerf_bkgd_backward_dgrad: n must be >= 1");
-  hipLaunchKernelGGL(bkgd_dgrad_kernel, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, (hipStream_t)stream, params, (const float*)save, d_out, (long long)n,
-                     (float)(1 + 2 * rgb_padding), (float)rgb_padding, (float*)dy, (float4*)d_dirs);
-  RNERF_CHECK_LAUNCH();
-  return RNERF_OK;
-}
-
-extern "C" int rnerf_bkgd_backward_wgrad(const void* save, void* dy, int64_t n, float* grads, int coresident, void* stream) {
-  RNERF_CHECK_ARG(save && dy && grads, "rnerf_bkgd_backward_wgrad: null pointer");
-  RNERF_CHECK_ARG(n >= 1, "rnerf_bkgd_backward_wgrad: n must be >= 1");
-  hipStream_t st = (hipStream_t)stream;
-  const float* sv = (const float*)save;
-  float* dyf = (float*)dy;
-  const unsigned chunks = (unsigned)((n + 255) / 256);
-  float* partial = dyf + (size_t)n * 5 * 128;
-  if (coresident)
-    hipLaunchKernelGGL(bkgd_wgrad_co_kernel<0>, dim3(chunks, 18, 2), dim3(64), 0, st, sv, (const float*)dyf, (long long)n, partial);
-  else
-    hipLaunchKernelGGL(bkgd_wgrad_kernel<0>, dim3(((chunks + 7) / 8) * 8 * SmallNet<0>::UNITS), dim3(256), 0, st, sv, (const float*)dyf, (long long)n, partial);
-  hipLaunchKernelGGL(bkgd_wgrad_reduce_kernel<RNERF_BKGDMLP_PARAMS>, dim3((RNERF_BKGDMLP_PARAMS + 255) / 256), dim3(256), 0, st, (const float*)partial, (int)chunks,
-                     grads);
-  RNERF_CHECK_LAUNCH();
-  return RNERF_OK;
+  return launch_bkgd16_fwd(true, params, dirs, dir_stride, (long long)n, (float)(1 + 2 * rgb_padding), (float)rgb_padding, out_rgb, (float*)save, (hipStream_t)stream);
 }
 
 extern "C" int rnerf_bkgd_backward(const float* params, const void* save, const float* d_out, int64_t n, double rgb_padding, void* dy,
                                    float* grads, float* d_dirs, void* stream) {
   RNERF_CHECK_ARG(params && save && d_out && dy && grads, "rnerf_bkgd_backward: null pointer");
-  int rc = rnerf_bkgd_backward_dgrad(params, save, d_out, n, rgb_padding, dy, d_dirs, stream);
-  if (rc != RNERF_OK) return rc;
-  return rnerf_bkgd_backward_wgrad(save, dy, n, grads, 0, stream);
+  RNERF_CHECK_ARG(n >= 1, "rnerf_bkgd_backward: n must be >= 1");
+  hipStream_t st = (hipStream_t)stream;
+  const float* sv = (const float*)save;
+  float* dyf = (float*)dy;
+  hipLaunchKernelGGL(bkgd_dgrad_kernel, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, st, params, sv, d_out, (long long)n, (float)(1 + 2 * rgb_padding),
+                     (float)rgb_padding, dyf, (float4*)d_dirs);
+  RNERF_CHECK_LAUNCH();
+  const unsigned chunks = (unsigned)((n + 255) / 256);
+  float* partial = dyf + (size_t)n * 5 * 128;
+  hipLaunchKernelGGL(bkgd_wgrad_kernel<0>, dim3(((chunks + 7) / 8) * 8 * SmallNet<0>::UNITS), dim3(256), 0, st, sv, (const float*)dyf, (long long)n, partial);
+  hipLaunchKernelGGL(bkgd_wgrad_reduce_kernel<RNERF_BKGDMLP_PARAMS>, dim3((RNERF_BKGDMLP_PARAMS + 255) / 256), dim3(256), 0, st, (const float*)partial, (int)chunks,
+                     grads);
+  RNERF_CHECK_LAUNCH();
+  return RNERF_OK;
 }
 
 extern "C" int rnerf_so3_query(const float* table, const rnerf_grid* g, const float* so3_params, const float* window10, const float* pts,

@@ -446,11 +446,10 @@ extern "C" int rnerf_forward(const rnerf_model* m, const float* origins, const f
 
 // ---- training --------------------------------------------------------------------------------------------------------------------
 namespace rnerf {
-static inline bool co_requested(const rnerf_train_cfg* c) { return c->aux_stream && c->coresident_bkgd_wgrad; }
 // hierarchical models with an aux stream: the two levels' backward passes side by side when together they are at most two rounds of row
 // tiles (see rnerf_train_forward_backward); also decides whether the workspace carries the coarse level's own dY / d raw / wgrad scratch
 static bool levels_side_by_side(const rnerf_model* m, const rnerf_train_cfg* c, int32_t B) {
-  if (m->num_fine <= 0 || !c->aux_stream || co_requested(c)) return false;
+  if (m->num_fine <= 0 || !c->aux_stream) return false;
   const int cus = current_device_cus();
   const long long tiles_both = ((long long)m->num_coarse * B + 255) / 256 + ((long long)(m->num_coarse + m->num_fine) * B + 255) / 256;
   return tiles_both <= 2LL * cus;
@@ -627,10 +626,11 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
   RNERF_TRY(rnerf_loss_reduce(Nf > 0 ? lc.rgb : nullptr, lf.rgb, lf.trans, lf.tb, pixels, B, t.sums, stream));
   const double bg_on = (c->bg_weight > 0 && c->annealed_alpha > 0) ? 1.0 : 0.0;
   const double mse_scale = 2.0 / (3.0 * B);
+  const double env_on = c->annealed_alpha > 0 ? 1.0 : 0.0;
   if (!aux) RNERF_CHECK_HIP(hipMemsetAsync(grads, 0, (size_t)(n_theta + 8) * sizeof(float), st));
-  // The next batch's march on the side stream, forked from `stream` at the call.  With beside_wgrad it is issued right before the LARGEST
-  // wgrad of the step (the fine level's when there is one): the wgrad keeps 64 registers free on every SIMD (WGRAD_VGPRS in mlp.hip), so the
-  // march's waves are co-resident with it and the whole march hides behind that HBM-paced kernel.
+  // The next batch's march on the side stream, forked from `stream` right before the LARGEST wgrad of the step (the fine level's when there
+  // is one): the wgrad keeps 64 registers free on every SIMD (WGRAD_VGPRS in mlp.hip), so the march's waves are co-resident with it and the
+  // whole march hides behind that HBM-paced kernel.
   auto march_next = [&]() -> int {
     RNERF_CHECK_ARG(next->origins && next->viewdirs && next->path_pd && next->path_dr && next->side_stream, "rnerf_train_forward_backward: incomplete rnerf_prefetch");
     RNERF_TRY(rnerf_fork(stream, next->side_stream));
@@ -648,8 +648,6 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
   // rounds: beyond that the kernels' static tile striding is delayed on the CUs the other level took first and the step gets SLOWER
   // (profiles/r04/levels_side_by_side.txt: 512 rays 2.28 -> 2.18 ms, 128 rays 1.50 -> 1.33; 1024 rays 3.36 -> 3.45, 4096 rays 11.9 -> 12.4).
   const bool split_levels = levels_side_by_side(m, c, B);
-  const bool bk_early = split_levels && !(aux && c->coresident_bkgd_wgrad);
-  void* bk2 = nullptr;      // the third stream, when the background backward went there
   float* d_raw_c = split_levels ? t.d_raw_c : t.d_raw;
   void* dy_c = split_levels ? t.dy_c : t.dy;
   if (Nf > 0) {
@@ -659,29 +657,19 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
       RNERF_TRY(rnerf_composite_backward(f.raw_c, path_pd, path_dr, jitter, Nc, B, bkgd, m->rgb_padding, m->sigma_bias, lc.rgb, pixels, nullptr, nullptr, nullptr,
                                          mse_scale, 0.0, d_raw_c, d_first, 1, m->white_bkgd, level_mask_mode(m), level_mask_box(m), stream));
       RNERF_TRY(rnerf_fork(stream, aux));
-      if (bk_early) {      // d loss / d background is final (both compositing backwards have run): its whole backward goes beside the NerfMLP
-        // chains — on the third stream when there is one (nothing waits behind it), else in front of the coarse level's on the aux stream.
-        // (Measured, profiles/r04/small_batches.txt: 256 rays 1.48 -> 1.39 ms, 512 rays the same, 128 rays 1.09 -> 1.11: with a
-        // quarter of the chip's tiles the coarse chain is not what the step waits for, and the third stream only adds its fork / join.)
-        const long long tiles_both = ((long long)Nc * B + 255) / 256 + ((long long)S * B + 255) / 256;
-        bk2 = (c->aux2_stream && tiles_both > current_device_cus() / 2) ? c->aux2_stream : nullptr;
-        void* bk = bk2 ? bk2 : aux;
-        if (bk2) RNERF_TRY(rnerf_fork(stream, bk));
-        const double env_on_ = c->annealed_alpha > 0 ? 1.0 : 0.0;
-        if (smooth) RNERF_TRY(rnerf_env_smooth_backward(rgb_env, ps, c->bg_smooth_weight * env_on_, t.d_all + (size_t)3 * B, t.env_sum, bk));
-        RNERF_TRY(rnerf_bkgd_backward(th_b, t.save_bk, t.d_all, (int64_t)B + M, m->rgb_padding, t.dy_bk, g_b, nullptr, bk));
-      }
+      // d loss / d background is final (both compositing backwards have run): its whole backward goes beside the NerfMLP chains, in front
+      // of the coarse level's on the aux stream
+      if (smooth) RNERF_TRY(rnerf_env_smooth_backward(rgb_env, ps, c->bg_smooth_weight * env_on, t.d_all + (size_t)3 * B, t.env_sum, aux));
+      RNERF_TRY(rnerf_bkgd_backward(th_b, t.save_bk, t.d_all, (int64_t)B + M, m->rgb_padding, t.dy_bk, g_b, nullptr, aux));
       RNERF_TRY(nerfmlp_dgrad_impl(t.packed_bwd, t.packed_c, prec, bwd, t.save_c, d_raw_c, (int64_t)Nc * B, dy_c, !pre_zeroed, false, (hipStream_t)aux));
       RNERF_TRY(rnerf_nerfmlp_wgrad(prec, bwd, t.save_c, dy_c, (int64_t)Nc * B, g_c, t.wgrad_ws_c, aux));
     }
     if (!aux) RNERF_TRY(rnerf_nerfmlp_pack_bwd(th_f, bwd, t.packed_bwd_f, stream));
     RNERF_TRY(nerfmlp_dgrad_impl(t.packed_bwd_f, t.packed_f, prec, bwd, t.save_f, t.d_raw, (int64_t)S * B, t.dy, !pre_zeroed, !split_levels, st));
-    if (next && next->beside_wgrad) RNERF_TRY(march_next());
+    if (next) RNERF_TRY(march_next());
     RNERF_TRY(rnerf_nerfmlp_wgrad(prec, bwd, t.save_f, t.dy, (int64_t)S * B, g_f, t.wgrad_ws, stream));
-    if (split_levels) {
+    if (split_levels)
       RNERF_TRY(rnerf_join(stream, aux));
-      if (bk2) RNERF_TRY(rnerf_join(stream, bk2));
-    }
     else
       RNERF_TRY(rnerf_composite_backward(f.raw_c, path_pd, path_dr, jitter, Nc, B, bkgd, m->rgb_padding, m->sigma_bias, lc.rgb, pixels, nullptr, nullptr, nullptr,
                                          mse_scale, 0.0, t.d_raw, d_first, 1, m->white_bkgd, level_mask_mode(m), level_mask_box(m), stream));
@@ -689,28 +677,13 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
     RNERF_TRY(rnerf_composite_backward(f.raw_c, path_pd, path_dr, jitter, Nc, B, bkgd, m->rgb_padding, m->sigma_bias, lf.rgb, pixels, lf.trans, lf.tb, t.sums,
                                        mse_scale, c->bg_weight * bg_on, t.d_raw, d_first, 0, m->white_bkgd, level_mask_mode(m), level_mask_box(m), stream));
   }
-  // (experiment, cfg->coresident_bkgd_wgrad: the background MLP's weight gradient as a co-resident kernel on the aux stream beside the
-  //  NerfMLP wgrad — its dgrad chain then runs here, ahead of the NerfMLP dgrad; measured neutral at bench size)
-  const double env_on = c->annealed_alpha > 0 ? 1.0 : 0.0;
-  const bool co = aux && c->coresident_bkgd_wgrad;
-  if (co) {
-    if (smooth) RNERF_TRY(rnerf_env_smooth_backward(rgb_env, ps, c->bg_smooth_weight * env_on, t.d_all + (size_t)3 * B, t.env_sum, stream));
-    RNERF_TRY(rnerf_bkgd_backward_dgrad(th_b, t.save_bk, t.d_all, (int64_t)B + M, m->rgb_padding, t.dy_bk, nullptr, stream));
-  }
   if (!aux) RNERF_TRY(rnerf_nerfmlp_pack_bwd(th_c, bwd, t.packed_bwd, stream));
   if (!split_levels)      // (a hierarchical model's coarse dgrad is the SECOND writer of t.dy here: it clears its own reference)
     RNERF_TRY(nerfmlp_dgrad_impl(t.packed_bwd, t.packed_c, prec, bwd, t.save_c, t.d_raw, (int64_t)Nc * B, t.dy, !(pre_zeroed && Nf == 0), true, st));
-  if (co) {      // forked HERE, not earlier: the NerfMLP dgrad owns every CU whole, the wgrad below leaves room for these waves
-    RNERF_TRY(rnerf_fork(stream, aux));
-    RNERF_TRY(rnerf_bkgd_backward_wgrad(t.save_bk, t.dy_bk, (int64_t)B + M, g_b, 1, aux));
-  }
-  if (next && next->beside_wgrad && Nf == 0) RNERF_TRY(march_next());
+  if (next && Nf == 0) RNERF_TRY(march_next());
   if (!split_levels) RNERF_TRY(rnerf_nerfmlp_wgrad(prec, bwd, t.save_c, t.dy, (int64_t)Nc * B, g_c, t.wgrad_ws, stream));
   if (c->grads_stream) RNERF_TRY(rnerf_fork(stream, c->grads_stream));      // the NerfMLP gradient segments are final: the caller's collective may start
-  if (next && !next->beside_wgrad) RNERF_TRY(march_next());     // beside the tail below (background-MLP backward, loss glue) and the update
-  if (co) {
-    RNERF_TRY(rnerf_join(stream, aux));
-  } else if (!bk_early) {
+  if (!split_levels) {
     if (smooth) RNERF_TRY(rnerf_env_smooth_backward(rgb_env, ps, c->bg_smooth_weight * env_on, t.d_all + (size_t)3 * B, t.env_sum, stream));
     RNERF_TRY(rnerf_bkgd_backward(th_b, t.save_bk, t.d_all, (int64_t)B + M, m->rgb_padding, t.dy_bk, g_b, nullptr, stream));
   }

@@ -156,8 +156,6 @@ class NerfModel:
         self._mlp_wg_limit = 0
         # whole_path: apply() goes through rnerf_forward (one C call per batch); False keeps the stage-by-stage host sequence (tests / taps)
         self.whole_path = True
-        # the next batch's march as co-resident waves of the wgrad (rnerf_prefetch.beside_wgrad); False queues it behind the wgrad (round 2's form)
-        self.march_beside_wgrad = True
         self._ws: Dict[Tuple[str, int], torch.Tensor] = {}
         self._key_cache: Dict[bytes, torch.Tensor] = {}
 
@@ -302,22 +300,13 @@ class NerfModel:
             t.record_stream(self._side)
         h = PathHandle(pd, dr, None, torch.cuda.Event(), B)
         h.keep = (o, v)
-        return h, _lib.Prefetch(o.data_ptr(), v.data_ptr(), pd.data_ptr(), dr.data_ptr(), self._side.cuda_stream,
-                                 int(self.march_beside_wgrad))
+        return h, _lib.Prefetch(o.data_ptr(), v.data_ptr(), pd.data_ptr(), dr.data_ptr(), self._side.cuda_stream)
 
     def tail_stream(self) -> torch.cuda.Stream:
         """The stream rnerf_train_forward_backward uses for work that is independent of the NerfMLP backward (rnerf_train_cfg.aux_stream)."""
         if getattr(self, "_tail", None) is None:
             self._tail = shared_stream(self.device, "tail")
         return self._tail
-
-    def tail2_stream(self) -> torch.cuda.Stream:
-        """A third stream of the train step (rnerf_train_cfg.aux2_stream): the background MLP's backward of a small hierarchical batch.
-        Opt-in (train._AUX2_STREAM, train.train_cfg): a fifth stream beside default / march / tail / comm no longer gets a hardware queue
-        of its own under the default GPU_MAX_HW_QUEUES=4."""
-        if getattr(self, "_tail2", None) is None:
-            self._tail2 = shared_stream(self.device, "tail2")
-        return self._tail2
 
     def comm_stream(self) -> torch.cuda.Stream:
         """The stream the train step's NerfMLP-gradient all-reduce is issued from (rnerf_train_cfg.grads_stream: ordered behind the last wgrad).

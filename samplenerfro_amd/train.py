@@ -33,9 +33,6 @@ from . import _lib, distributed, ops, prng
 from .models import BKGD_MLP_SHAPES, NERF_MLP_SHAPES, SO3_MLP_SHAPES, NerfModel, make_variables
 from .utils import Rays, Stats, learning_rate_decay
 
-# Switches of the step's stream placement: module attributes, never environment reads.
-_AUX2_STREAM = False                    # a third stream for the background backward of small hierarchical batches (see train_cfg)
-_CORESIDENT_BKGD_WGRAD = False          # the background-MLP weight gradient as a co-resident kernel beside the NerfMLP wgrad (see train_cfg)
 _RANGE_RETRY_LAG = 2                    # range_retry="lag": the count of step k - 2 is read after step k has been queued (train_step)
 _LAG_SLOTS = 8
 _SKIP_NONFINITE_UPDATES = True          # rnerf_adam_cfg.skip_nonfinite: an update with an inf / NaN gradient entry is skipped and counted (train_step)
@@ -280,15 +277,6 @@ def train_cfg(model: NerfModel, state: TrainState, flags, annealed: float) -> "_
     # the second stream of rnerf_train_cfg: what depends on the parameters only (operand packing, zeroing the gradient buffer, sum theta^2)
     # runs there beside the head of the step
     c.aux_stream = model.tail_stream().cuda_stream
-    # a third stream for the background backward of small hierarchical batches: opt-in.  It pays at 256 rays (1.48 -> 1.39 ms) when it
-    # gets a hardware queue of its own, and costs 30 % when it lands on the queue of the march or of the main stream — which is decided by
-    # how many streams the process has created (GPU_MAX_HW_QUEUES = 4)
-    if _AUX2_STREAM:
-        c.aux2_stream = model.tail2_stream().cuda_stream
-    # _CORESIDENT_BKGD_WGRAD (experiment, off): the background-MLP weight gradient as a co-resident kernel beside the NerfMLP wgrad.  Measured
-    # neutral at 4096 x 128 (what it saves on the critical path, ~0.12 ms, the wgrad loses to the extra waves: 2.04 -> 2.2-2.4 ms),
-    # +1-2 % at 1024 rays x (64 + 128)
-    c.coresident_bkgd_wgrad = int(_CORESIDENT_BKGD_WGRAD)
     return c
 
 

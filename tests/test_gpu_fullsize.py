@@ -408,7 +408,7 @@ def test_config3_ship_refractive_full_size_sample():
 
 def test_march_coresident_with_the_wgrad_changes_no_bit(world):
     """The product train step at bench size (4096 x 128 flat, 512^3): the next batch's march is forked right before the NerfMLP wgrad and
-    runs co-resident with it on every CU (rnerf_prefetch.beside_wgrad; the wgrad is held to 224 registers for that).  Sharing SIMDs must
+    runs co-resident with it on every CU (rnerf_prefetch; the wgrad is held to 224 registers for that).  Sharing SIMDs must
     change nothing: the prefetched path record equals a stand-alone march of the same rays bit for bit, and the step's gradient equals the
     gradient of the same step issued without any prefetch."""
     from samplenerfro_amd import ops, utils

@@ -205,9 +205,6 @@ def test_bkgd_mlp_out_of_range_is_never_silent(scene):
     """The background MLP runs on f16 hi + lo operands (weights x 2^8): a weight >= 256 or an activation above 65504 is outside that
     arithmetic.  The outputs are then NaN — never finite, plausible colours (the ReLU keeps NaN; same contract as the NerfMLP engines)."""
     from samplenerfro_amd import ops
-    import os
-    if os.environ.get("RNERF_BKGD_EXACT") == "1":
-        pytest.skip("the exact-fp32 kernels have no f16 range")
     pf = syn.init_params_flat(3, bias_scale=0.1)["bkgd_mlp"].copy()
     rng = np.random.default_rng(4)
     dirs = R.safe_l2_normalize(rng.standard_normal((300, 3)).astype(F32))
