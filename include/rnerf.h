@@ -476,11 +476,13 @@ typedef struct rnerf_train_cfg {
   int64_t frozen_count;
   void* aux_stream;            /* nullable: a second stream.  Everything of a step that depends on the parameters only — packing the operand streams of
                                   both directions, zeroing the gradient buffer, sum theta^2 — runs there beside the key kernels, the march and the
-                                  background-MLP forward, and is joined inside the call before the first NerfMLP kernel */
+                                  background-MLP forward, and is joined inside the call before the first NerfMLP kernel.  At the other end of
+                                  the step the env-map term, the background-MLP backward and the statistics run there, beside the last NerfMLP
+                                  wgrad instead of behind it, joined before the call returns (the same kernels on the same operands: same bits).
+                                  May be the same stream as grads_stream */
   void* grads_stream;          /* nullable: a stream the call orders behind the LAST NerfMLP wgrad (rnerf_fork at that point).  grads[0 .. NerfMLP
                                   segments) are final there: a caller with more than one rank starts their all-reduce (jax.lax.pmean, train.py:166 —
-                                  95 % of the bytes) on this stream as soon as the call returns, beside the background-MLP backward and the loss tail
-                                  still queued on `stream`, and joins before rnerf_adam_update */
+                                  95 % of the bytes) on this stream as soon as the call returns, and joins before rnerf_adam_update */
 } rnerf_train_cfg;
 /* The march of the NEXT batch (it reads neither the parameters nor anything of this step): when `next` is given, its rays are marched on
  * next->side_stream, forked from `stream` right before the last NerfMLP wgrad, so that the latency-bound march runs as co-resident waves
@@ -522,6 +524,15 @@ typedef struct rnerf_adam_cfg {
 } rnerf_adam_cfg;
 int rnerf_adam_update(const rnerf_adam_cfg* c, float* theta, float* mu, float* nu, float* grads, int64_t n_theta, const float* frozen_params,
                       int64_t n_frozen, int32_t* step_counter, float* scratch, void* stream);
+/* The same update — the same bits in theta, mu, nu, grads, scratch[0..3] and the step counter — in two dependent launches instead of
+ * three: the kernel that applies the update forms the scalars (learning rate, bias corrections, clip multiplier, non-finite count) in
+ * every block from the per-block partials, with the additions rnerf_adam_update's one-workgroup launch performs.  (A configuration
+ * without decay, clip and skip_nonfinite has no partials launch and keeps rnerf_adam_update's sequence.)  nonfinite_out (nullable): a
+ * device-visible address, e.g. pinned host memory, that receives scratch[3] from the same launch — the word a host reads later without a
+ * copy launch behind every step. */
+int rnerf_adam_update_fused(const rnerf_adam_cfg* c, float* theta, float* mu, float* nu, float* grads, int64_t n_theta,
+                            const float* frozen_params, int64_t n_frozen, int32_t* step_counter, float* scratch, float* nonfinite_out,
+                            void* stream);
 
 /* ---- one launch graph per step (hipGraph): begin capture on `stream`, issue any sequence of the calls above on it (and on streams forked
  * from it through rnerf_fork / rnerf_join), end -> an executable graph that replays the whole sequence with one launch. */

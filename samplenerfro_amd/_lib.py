@@ -147,6 +147,7 @@ SIGNATURES = {
     "rnerf_train_workspace_bytes": (C.c_size_t, [_MP, _TP, _i32]),
     "rnerf_train_forward_backward": (C.c_int, [_MP, _TP, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, C.POINTER(Prefetch), _vp]),
     "rnerf_adam_update": (C.c_int, [_AP, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "rnerf_adam_update_fused": (C.c_int, [_AP, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "rnerf_graph_begin": (C.c_int, [_vp]),
     "rnerf_graph_end": (C.c_int, [_vp, C.POINTER(C.c_void_p)]),
     "rnerf_graph_launch": (C.c_int, [_vp, _vp]),

@@ -179,7 +179,8 @@ constexpr int ADAM_BLOCKS = 1024;
 // g <- clip_value(g + wd2 * theta); partial sums of g^2 per block (deterministic two-level reduction, no float atomics) and, per block, the
 // number of non-finite entries BEFORE the value clip (fminf / fmaxf would turn a NaN into +-max_val: a silent, wrong, finite gradient)
 __global__ void __launch_bounds__(256) adam_prep_kernel(const float* __restrict__ theta, float* __restrict__ g, long long n, float wd2, float max_val,
-                                                        int want_norm, float* __restrict__ partial, float* __restrict__ bad_partial) {
+                                                        int want_norm, float* __restrict__ partial, float* __restrict__ bad_partial,
+                                                        int* __restrict__ step_inc) {
   float s = 0.f;
   int bad = 0;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
@@ -199,6 +200,9 @@ __global__ void __launch_bounds__(256) adam_prep_kernel(const float* __restrict_
   if (threadIdx.x == 0) {
     if (want_norm) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
     bad_partial[blockIdx.x] = (float)((redb[0] + redb[1]) + (redb[2] + redb[3]));
+    // the fused sequence (rnerf_adam_update_fused): the step counter is incremented HERE, by the one thread of this launch that touches it,
+    // and adam_apply_fused_kernel's blocks all read *step - 1 in the next launch — never a read and the increment in the same launch
+    if (step_inc && blockIdx.x == 0) *step_inc = *step_inc + 1;
   }
 }
 // the frozen variables' gradient is their weight-decay term (jax.grad returns it although their optimiser label is "zero")
@@ -220,9 +224,11 @@ struct AdamSched { double lr_init, lr_final, lr_delay_mult, max_steps, lr_delay_
 // scal[0] = -lr / (1 - b1^t), scal[1] = 1 / (1 - b2^t) (or -1: this update is skipped), scal[2] = norm-clip multiplier, scal[3] = the
 // non-finite entries adam_prep_kernel counted (bad_partial; nullptr: adam_apply_kernel counts); the step counter is incremented.
 // learning_rate_decay: rnerf/utils.py:490-528 in float64 like the host version.
-__global__ void __launch_bounds__(256) adam_scalars_kernel(AdamSched c, int* __restrict__ step, const float* __restrict__ partial, int n_partial,
-                                                           const float* __restrict__ bad_partial, float* __restrict__ scal) {
-  __shared__ double red[256];
+// The body of the scalars step, for one 256-thread workgroup: out[0..3] (thread 0 only) from the update count `count`.  adam_scalars_kernel
+// and adam_apply_fused_kernel both run exactly this — the same strided per-thread sums in double, the same tree, the same float64 schedule
+// — so the four scalars are the same bits whichever launch forms them, and the same in every block of the fused one.
+__device__ __forceinline__ void adam_scalars_block(const AdamSched& c, int count, const float* __restrict__ partial, int n_partial,
+                                                   const float* __restrict__ bad_partial, double* red, float* out) {
   double s = 0.0;
   for (int i = threadIdx.x; i < n_partial; i += 256) s += (double)partial[i];
   red[threadIdx.x] = s;
@@ -236,7 +242,6 @@ __global__ void __launch_bounds__(256) adam_scalars_kernel(AdamSched c, int* __r
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
   if (threadIdx.x != 0) return;
-  const int count = *step;
   const double t = (double)count + 1.0;
   double lr;
   if (c.use_override) {          // an explicit flag, not "lr > 0": a schedule that returns exactly 0.0 (warm-up, count 0) is a zero step
@@ -252,16 +257,22 @@ __global__ void __launch_bounds__(256) adam_scalars_kernel(AdamSched c, int* __r
     lr = start * delay * exp(log(c.lr_init) * (1.0 - tt) + log(c.lr_final) * tt);
   }
   const double bad = red[0];
-  scal[0] = (float)(-lr / (1.0 - pow(c.b1, t)));
-  scal[1] = (c.skip_nonfinite && bad > 0.0) ? -1.0f : (float)(1.0 / (1.0 - pow(c.b2, t)));      // -1: adam_apply leaves theta, mu, nu alone
+  out[0] = (float)(-lr / (1.0 - pow(c.b1, t)));
+  out[1] = (c.skip_nonfinite && bad > 0.0) ? -1.0f : (float)(1.0 / (1.0 - pow(c.b2, t)));      // -1: adam_apply leaves theta, mu, nu alone
   float mult = 1.0f;
   if (c.max_norm > 0) {
     const float norm = sqrtf((float)sumsq);
     mult = fminf((float)c.max_norm / (1e-7f + norm), 1.0f);             // train.py:174-180
   }
-  scal[2] = mult;
-  scal[3] = (float)bad;   // (no count from adam_prep: 0, and adam_apply counts the non-finite gradient entries of this update here)
-  *step = count + 1;      // a skipped update still counts: the schedule and the host's step number go on
+  out[2] = mult;
+  out[3] = (float)bad;    // (no count from adam_prep: 0, and adam_apply counts the non-finite gradient entries of this update here)
+}
+__global__ void __launch_bounds__(256) adam_scalars_kernel(AdamSched c, int* __restrict__ step, const float* __restrict__ partial, int n_partial,
+                                                           const float* __restrict__ bad_partial, float* __restrict__ scal) {
+  __shared__ double red[256];
+  const int count = *step;
+  adam_scalars_block(c, count, partial, n_partial, bad_partial, red, scal);
+  if (threadIdx.x == 0) *step = count + 1;      // a skipped update still counts: the schedule and the host's step number go on
 }
 // optax.scale_by_adam + scale_by_schedule: mu, nu, theta updated in place
 __global__ void __launch_bounds__(256) adam_apply_kernel(float* __restrict__ theta, float* __restrict__ mu, float* __restrict__ nu,
@@ -281,6 +292,34 @@ __global__ void __launch_bounds__(256) adam_apply_kernel(float* __restrict__ the
   if (count_bad && __builtin_amdgcn_ballot_w64(bad != 0) != 0) {    // (never taken on finite gradients)
     for (int o = 32; o > 0; o >>= 1) bad += __shfl_down(bad, o);
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&scal[3], (float)bad);
+  }
+}
+
+// adam_scalars_kernel + adam_apply_kernel in one launch, behind adam_prep_kernel (which has incremented *step): every block forms the four
+// scalars itself from the ADAM_BLOCKS partials (8 KB from L2 per block, the additions of adam_scalars_block: the same bits in every block),
+// then applies its share.  Block 0 writes scal[0..3] for the host-side readers — no block READS scal in this launch — and, when given, the
+// non-finite count to `count_out` (device-visible pinned host memory: the word train.py's lagged range retry reads two steps later).
+__global__ void __launch_bounds__(256) adam_apply_fused_kernel(AdamSched c, const int* __restrict__ step, const float* __restrict__ partial,
+                                                               int n_partial, const float* __restrict__ bad_partial, float* __restrict__ theta,
+                                                               float* __restrict__ mu, float* __restrict__ nu, const float* __restrict__ g,
+                                                               long long n, float b1, float b2, float eps, float* __restrict__ scal,
+                                                               float* __restrict__ count_out) {
+  __shared__ double red[256];
+  __shared__ float sc[4];
+  adam_scalars_block(c, *step - 1, partial, n_partial, bad_partial, red, sc);
+  __syncthreads();
+  const float a = sc[0], c2 = sc[1], mult = sc[2];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    scal[0] = a; scal[1] = c2; scal[2] = mult; scal[3] = sc[3];
+    if (count_out) *count_out = sc[3];
+  }
+  if (c2 < 0.f) return;                                // rnerf_adam_cfg.skip_nonfinite and a non-finite gradient entry: no update
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const float gi = g[i] * mult;
+    const float m = mu[i] * b1 + gi * (1.0f - b1);
+    const float v = nu[i] * b2 + (gi * gi) * (1.0f - b2);
+    mu[i] = m; nu[i] = v;
+    theta[i] = theta[i] + a * (m / (sqrtf(v * c2) + eps));
   }
 }
 
@@ -681,22 +720,37 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
   if (!split_levels)      // (a hierarchical model's coarse dgrad is the SECOND writer of t.dy here: it clears its own reference)
     RNERF_TRY(nerfmlp_dgrad_impl(t.packed_bwd, t.packed_c, prec, bwd, t.save_c, t.d_raw, (int64_t)Nc * B, t.dy, !(pre_zeroed && Nf == 0), true, st));
   if (next && Nf == 0) RNERF_TRY(march_next());
-  if (!split_levels) RNERF_TRY(rnerf_nerfmlp_wgrad(prec, bwd, t.save_c, t.dy, (int64_t)Nc * B, g_c, t.wgrad_ws, stream));
-  if (c->grads_stream) RNERF_TRY(rnerf_fork(stream, c->grads_stream));      // the NerfMLP gradient segments are final: the caller's collective may start
+  // The tail of the step that does not touch the NerfMLP gradients: the env-map term, the background MLP's whole backward and the
+  // statistics read d_all / save_bk / rgb_env / sums only and write g_b, env_sum, dy_bk and stats8.  With an aux stream (idle since the
+  // head of the step) they are queued there behind the last DGRAD launch — not behind the compositing backward: small workgroups that
+  // take CUs ahead of the persistent dgrad delay its static tile striding on every CU they sat on (profiles/r04/levels_side_by_side.txt)
+  // — so they become ready together with the last wgrad and run as co-resident waves beside it, like the march, instead of behind it:
+  // 0.13 ms of dependent small launches leave the end of the step, the wgrad pays 0.05 ms for the company (profiles/step_chain/).
+  // Order of execution only: no kernel and no operand changes.
+  const bool tail_on_aux = aux && !split_levels;
+  void* tail = tail_on_aux ? aux : stream;
+  if (tail_on_aux) RNERF_TRY(rnerf_fork(stream, aux));
+  if (!split_levels && !tail_on_aux) RNERF_TRY(rnerf_nerfmlp_wgrad(prec, bwd, t.save_c, t.dy, (int64_t)Nc * B, g_c, t.wgrad_ws, stream));
+  if (!tail_on_aux && c->grads_stream) RNERF_TRY(rnerf_fork(stream, c->grads_stream));      // the NerfMLP gradient segments are final: the caller's collective may start
   if (!split_levels) {
-    if (smooth) RNERF_TRY(rnerf_env_smooth_backward(rgb_env, ps, c->bg_smooth_weight * env_on, t.d_all + (size_t)3 * B, t.env_sum, stream));
-    RNERF_TRY(rnerf_bkgd_backward(th_b, t.save_bk, t.d_all, (int64_t)B + M, m->rgb_padding, t.dy_bk, g_b, nullptr, stream));
+    if (smooth) RNERF_TRY(rnerf_env_smooth_backward(rgb_env, ps, c->bg_smooth_weight * env_on, t.d_all + (size_t)3 * B, t.env_sum, tail));
+    RNERF_TRY(rnerf_bkgd_backward(th_b, t.save_bk, t.d_all, (int64_t)B + M, m->rgb_padding, t.dy_bk, g_b, nullptr, tail));
   }
   RNERF_TRY(rnerf_train_stats(t.sums, B, Nf > 0, c->bg_weight * bg_on, smooth ? t.env_sum : nullptr, ps, env_on, aux ? nullptr : theta, n_theta, c->frozen_sq,
-                              n_theta + c->frozen_count, stats8, stream));
+                              n_theta + c->frozen_count, stats8, tail));
+  if (tail_on_aux) {
+    RNERF_TRY(rnerf_nerfmlp_wgrad(prec, bwd, t.save_c, t.dy, (int64_t)Nc * B, g_c, t.wgrad_ws, stream));
+    if (c->grads_stream) RNERF_TRY(rnerf_fork(stream, c->grads_stream));
+    RNERF_TRY(rnerf_join(stream, aux));      // g_b and stats8 are final for whatever the caller queues on `stream` (its second all-reduce, the optimiser)
+  }
   return RNERF_OK;
 }
 
-extern "C" int rnerf_adam_update(const rnerf_adam_cfg* c, float* theta, float* mu, float* nu, float* grads, int64_t n_theta, const float* frozen_params,
-                                 int64_t n_frozen, int32_t* step_counter, float* scratch, void* stream) {
-  RNERF_CHECK_ARG(c && theta && mu && nu && grads && step_counter && scratch, "rnerf_adam_update: null pointer");
-  RNERF_CHECK_ARG(n_theta >= 1 && c->n_all >= n_theta, "rnerf_adam_update: need n_theta >= 1 and n_all >= n_theta");
-  hipStream_t st = (hipStream_t)stream;
+// fused: prep (which increments the step counter) + adam_apply_fused_kernel — two launches — whenever the prep launch runs; without it
+// (no decay, no clip, no skip: adam_apply_kernel counts the non-finite entries into scal[3] with atomics, which cannot share a launch with
+// the block that initialises scal[3]) and for fused == false the sequence is prep, scalars, apply.
+static int adam_update_impl(const rnerf_adam_cfg* c, float* theta, float* mu, float* nu, float* grads, int64_t n_theta, const float* frozen_params,
+                            int64_t n_frozen, int32_t* step_counter, float* scratch, bool fused, float* count_out, hipStream_t st) {
   const double wd2 = c->weight_decay_mult > 0 ? 2.0 * c->weight_decay_mult / (double)c->n_all : 0.0;
   const int want_norm = c->grad_max_norm > 0;
   float* scal = scratch;                      // [0..3]
@@ -706,7 +760,7 @@ extern "C" int rnerf_adam_update(const rnerf_adam_cfg* c, float* theta, float* m
   if (wd2 != 0.0 || c->grad_max_val > 0 || want_norm || c->skip_nonfinite) {
     bad_partial = scratch + 4 + 2 * ADAM_BLOCKS;
     hipLaunchKernelGGL(adam_prep_kernel, dim3(ADAM_BLOCKS), dim3(256), 0, st, (const float*)theta, grads, (long long)n_theta, (float)wd2, (float)c->grad_max_val,
-                       want_norm, partial, bad_partial);
+                       want_norm, partial, bad_partial, fused ? step_counter : nullptr);
     if (want_norm) {
       n_partial = ADAM_BLOCKS;
       if (frozen_params && n_frozen > 0 && wd2 != 0.0) {
@@ -718,11 +772,32 @@ extern "C" int rnerf_adam_update(const rnerf_adam_cfg* c, float* theta, float* m
   }
   AdamSched s{c->lr_init, c->lr_final, c->lr_delay_mult, (double)c->max_steps, (double)c->lr_delay_steps, c->b1, c->b2, c->grad_max_norm, c->lr_override, c->use_lr_override != 0,
               c->skip_nonfinite != 0};
+  if (fused && bad_partial) {
+    hipLaunchKernelGGL(adam_apply_fused_kernel, dim3(ADAM_BLOCKS), dim3(256), 0, st, s, (const int*)step_counter, (const float*)partial, n_partial,
+                       (const float*)bad_partial, theta, mu, nu, (const float*)grads, (long long)n_theta, (float)c->b1, (float)c->b2, (float)c->eps, scal, count_out);
+    RNERF_CHECK_LAUNCH();
+    return RNERF_OK;
+  }
   hipLaunchKernelGGL(adam_scalars_kernel, dim3(1), dim3(256), 0, st, s, step_counter, (const float*)partial, n_partial, (const float*)bad_partial, scal);
   hipLaunchKernelGGL(adam_apply_kernel, dim3(ADAM_BLOCKS), dim3(256), 0, st, theta, mu, nu, (const float*)grads, (long long)n_theta, (float)c->b1, (float)c->b2,
                      (float)c->eps, scal, bad_partial == nullptr);
   RNERF_CHECK_LAUNCH();
+  if (count_out) RNERF_CHECK_HIP(hipMemcpyAsync(count_out, scal + 3, sizeof(float), hipMemcpyDefault, st));
   return RNERF_OK;
+}
+
+extern "C" int rnerf_adam_update(const rnerf_adam_cfg* c, float* theta, float* mu, float* nu, float* grads, int64_t n_theta, const float* frozen_params,
+                                 int64_t n_frozen, int32_t* step_counter, float* scratch, void* stream) {
+  RNERF_CHECK_ARG(c && theta && mu && nu && grads && step_counter && scratch, "rnerf_adam_update: null pointer");
+  RNERF_CHECK_ARG(n_theta >= 1 && c->n_all >= n_theta, "rnerf_adam_update: need n_theta >= 1 and n_all >= n_theta");
+  return adam_update_impl(c, theta, mu, nu, grads, n_theta, frozen_params, n_frozen, step_counter, scratch, false, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int rnerf_adam_update_fused(const rnerf_adam_cfg* c, float* theta, float* mu, float* nu, float* grads, int64_t n_theta, const float* frozen_params,
+                                       int64_t n_frozen, int32_t* step_counter, float* scratch, float* nonfinite_out, void* stream) {
+  RNERF_CHECK_ARG(c && theta && mu && nu && grads && step_counter && scratch, "rnerf_adam_update_fused: null pointer");
+  RNERF_CHECK_ARG(n_theta >= 1 && c->n_all >= n_theta, "rnerf_adam_update_fused: need n_theta >= 1 and n_all >= n_theta");
+  return adam_update_impl(c, theta, mu, nu, grads, n_theta, frozen_params, n_frozen, step_counter, scratch, true, nonfinite_out, (hipStream_t)stream);
 }
 
 // ---- hipGraph --------------------------------------------------------------------------------------------------------------------

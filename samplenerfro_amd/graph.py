@@ -147,9 +147,9 @@ class GraphTrainStep:
         s = self.state
         fs = frozen_sq_of(s, s.variables)
         frozen = s.variables["flat"].get("so3_mlp") if fs[1] > 0 else None
-        _lib.check(self.lib.rnerf_adam_update(C.byref(self.a), s.theta.data_ptr(), s.mu.data_ptr(), s.nu.data_ptr(), s.grads.data_ptr(), s.theta.numel(),
-                                              _lib.ptr(frozen), fs[1], s.step_dev.data_ptr(), s.adam_scratch.data_ptr(), self.main.cuda_stream),
-                   "rnerf_adam_update")
+        _lib.check(self.lib.rnerf_adam_update_fused(C.byref(self.a), s.theta.data_ptr(), s.mu.data_ptr(), s.nu.data_ptr(), s.grads.data_ptr(), s.theta.numel(),
+                                                    _lib.ptr(frozen), fs[1], s.step_dev.data_ptr(), s.adam_scratch.data_ptr(), None, self.main.cuda_stream),
+                   "rnerf_adam_update_fused")
 
     def _capture(self, slot: int):
         lib, st, sd = self.lib, self.main.cuda_stream, self.side.cuda_stream

@@ -67,6 +67,8 @@ class TrainState:
         self._lag_pending = []         # range_retry="lag": the steps whose non-finite count has not been looked at yet (at most _RANGE_RETRY_LAG)
         self._lag_host = torch.zeros(_LAG_SLOTS, dtype=torch.float32).pin_memory() if theta.is_cuda else None
         self._lag_count = 0
+        self._lag_word = None          # address of the _lag_host slot the update of the step being issued writes its non-finite count to
+        self._lag_word_written = False
         self.last_retry_stats = None
 
     def nonfinite_grads(self) -> int:
@@ -305,8 +307,13 @@ def _adam_update_on_device(state: TrainState, flags) -> None:
     state.sync_step_counter()
     fs = frozen_sq_of(state, state.variables)
     frozen = state.variables["flat"].get("so3_mlp") if fs[1] > 0 else None
-    _lib.check(lib.rnerf_adam_update(C.byref(a), state.theta.data_ptr(), state.mu.data_ptr(), state.nu.data_ptr(), state.grads.data_ptr(), state.theta.numel(),
-                                     _lib.ptr(frozen), fs[1], state.step_dev.data_ptr(), state.adam_scratch.data_ptr(), _lib.current_stream()), "rnerf_adam_update")
+    # two dependent launches (rnerf_adam_update_fused: rnerf_adam_update's bits); the lagged range retry's host word is written by the update itself
+    word = getattr(state, "_lag_word", None)
+    _lib.check(lib.rnerf_adam_update_fused(C.byref(a), state.theta.data_ptr(), state.mu.data_ptr(), state.nu.data_ptr(), state.grads.data_ptr(),
+                                           state.theta.numel(), _lib.ptr(frozen), fs[1], state.step_dev.data_ptr(), state.adam_scratch.data_ptr(),
+                                           word, _lib.current_stream()), "rnerf_adam_update_fused")
+    if word is not None:
+        state._lag_word_written = True
     state.step += 1
     state._step_dev_value = state.step
     state._staged_bad = None
@@ -352,8 +359,8 @@ def _train_step_whole(model: NerfModel, rng, state: TrainState, batch, flags, ji
     if next_rays is not None:
         next_path, nxt = model.prefetch_slot(next_rays)
     # jax.lax.pmean of gradients and stats (train.py:166-167).  With more than one rank the NerfMLP segments (95 % of the bytes) start their
-    # all-reduce on a side stream the call orders behind the last wgrad, beside the background-MLP backward and the loss tail still queued
-    # on the main stream; the background-MLP gradients and the stats follow in a small second one.
+    # all-reduce on a side stream the call orders behind the last wgrad; the background-MLP gradients and the stats (computed on the aux
+    # stream beside that wgrad, joined inside the call) follow in a small second one.
     comm = model.comm_stream() if (distributed.active() and hasattr(model, "comm_stream")) else None
     if comm is not None:
         c = _lib.TrainCfg.from_buffer_copy(c)          # (train_cfg results may be shared: the stream is this call's)
@@ -433,10 +440,17 @@ def train_step(model: NerfModel, rng, state: TrainState, batch: Dict[str, Any], 
             # a tapped step is looked at now, not re-run later (range_retry=True does both); inside a stream capture there is no host to decide
             return _train_step_once(model, rng, state, batch, flags, **kw)
         ctx = _dist_context()
-        out = _train_step_once(model, rng, state, batch, flags, **kw)
         slot = state._lag_count % _LAG_SLOTS
         state._lag_count += 1
-        state._lag_host[slot:slot + 1].copy_(state.adam_scratch[3:4], non_blocking=True)      # behind this step's update, on its stream
+        # the count goes to the pinned host word from the update's own launch (no copy launch behind the step); the staged sequence, whose
+        # update is not that call, copies it
+        state._lag_word, state._lag_word_written = state._lag_host[slot:slot + 1].data_ptr(), False
+        try:
+            out = _train_step_once(model, rng, state, batch, flags, **kw)
+        finally:
+            state._lag_word = None
+        if not state._lag_word_written:
+            state._lag_host[slot:slot + 1].copy_(state.adam_scratch[3:4], non_blocking=True)      # behind this step's update, on its stream
         ev = torch.cuda.Event(); ev.record()
         replay = dict(kw, next_rays=None, path=None)                 # (the marched path of that step may be overwritten by then: marched again)
         # the re-run happens two steps later: it must see THIS step's batch even when the caller's loader refills its staging tensors in
