@@ -37,7 +37,8 @@ extern "C" {
  * stream (rnerf_nerfmlp_packed_bytes grew) — and this round's additions: enum rnerf_backward gains F16X3_LO8, rnerf_sample_batch.
  * 4: the opt-in schedule fields no caller set are gone.  rnerf_train_cfg ends with aux_stream, grads_stream (nothing in between);
  * rnerf_prefetch ends with side_stream (the march always forks right before the last NerfMLP wgrad); rnerf_bkgd_backward is the only
- * background-MLP backward entry point. */
+ * background-MLP backward entry point.  Still 4 with rnerf_flip / rnerf_flip_workspace_bytes: they are appended, no existing entry
+ * point or struct moved. */
 #define RNERF_VERSION 4
 
 enum rnerf_status {
@@ -557,6 +558,22 @@ int rnerf_join(void* main_stream, void* side_stream);
 size_t rnerf_ssim_workspace_bytes(int64_t n, int32_t H, int32_t W, int32_t C, int32_t filter_size);
 int rnerf_ssim(const float* img0, const float* img1, int64_t n, int32_t H, int32_t W, int32_t C, int32_t filter_size, double filter_sigma,
                double max_val, double k1, double k2, float* map, float* mean, void* workspace, void* stream);
+
+/* ---- Evaluation: LDR-FLIP.  compute_ldrflip (metric/flip/flip_api.py:439-495) as metric/summary.py:72-78 calls it, on the device.
+ * reference, test: float[n][H][W][3] (channels last, sRGB nominally in [0, 1]); map (nullable): float[n][H][W] (the filters replicate the
+ * border); mean (nullable, not both null): float[n], the mean of each image's map.  pixels_per_degree (finite, > 0) sets the filters:
+ * the spatial CSFs of generate_spatial_filter, radius r_s = ceil(3 sqrt(0.04 / (2 pi^2)) ppd), and the edge / point detectors of
+ * feature_detection, radius r_f = ceil(3 * 0.5 * 0.082 ppd) <= r_s; their 1-D factors are computed on the host in double (the squared
+ * distance rounded to float32 as there) and rounded to float once.  67.02 (compute_ldrflip's default) gives radii 10 and 9, 4.189
+ * (summary.py) gives 1 and 1.  Both images go through one instruction sequence: where they agree on every pixel within r_s (border
+ * replicated) of a pixel, the map there is exactly 0.  A NaN pixel makes NaN the map within r_s of it and that image's mean.
+ * `workspace` (rnerf_flip_workspace_bytes, 8-byte aligned, always needed) holds one fp64 partial per 16 x 64 tile,
+ * 8 n ceil(H / 16) ceil(W / 64) bytes, then 14 filtered planes, 56 n H W bytes; the mean is a fixed-order fp64 sum: the same inputs give
+ * the same bits on every run.  RNERF_ERR_UNSUPPORTED when r_s > 15 (ppd above about 111) or when ppd is so small (below about 0.65) that
+ * the detectors' off-centre weights vanish; the workspace query then returns 0. */
+size_t rnerf_flip_workspace_bytes(int64_t n, int32_t H, int32_t W, double pixels_per_degree);
+int rnerf_flip(const float* reference, const float* test, int64_t n, int32_t H, int32_t W, double pixels_per_degree, float* map,
+               float* mean, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

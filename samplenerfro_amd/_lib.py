@@ -157,6 +157,8 @@ SIGNATURES = {
     # evaluation (csrc/metrics.hip)
     "rnerf_ssim_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32, _i32, _i32]),
     "rnerf_ssim": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp]),
+    "rnerf_flip_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32, _dbl]),
+    "rnerf_flip": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _dbl, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

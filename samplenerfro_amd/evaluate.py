@@ -2,7 +2,8 @@
 
 `device_views` yields the batches eval.py reads ({"rays", "pixels"}) with the rays generated on the device; `evaluate` renders each view
 with utils.render_image (pipelined form), scores it on the device — PSNR of the device MSE (utils.compute_psnr) and SSIM with max_val 1
-(utils.compute_ssim, rnerf_ssim) — and reads back two floats per view.  With save_output it writes the reference's files.
+(utils.compute_ssim, rnerf_ssim) — and reads back two floats per view.  With save_output it writes the reference's files.  With flip=True
+each view is also scored with LDR-FLIP (utils.compute_flip, rnerf_flip; metric/summary.py:72-78) and the read-back carries three floats.
 """
 from __future__ import annotations
 
@@ -34,8 +35,9 @@ def device_views(images, camtoworlds, *, focal: Optional[float] = None, cam_mat=
         yield {"rays": Rays(o, None, v, None), "pixels": pix}
 
 
-def write_metric_files(out_dir: str, step, psnr_values, ssim_values) -> None:
-    """eval.py:207-215: psnrs_{step}.txt / ssims_{step}.txt (the values joined by spaces) and psnr.txt / ssim.txt (their means)."""
+def write_metric_files(out_dir: str, step, psnr_values, ssim_values, flip_values=None) -> None:
+    """eval.py:207-215: psnrs_{step}.txt / ssims_{step}.txt (the values joined by spaces) and psnr.txt / ssim.txt (their means).  With
+    flip_values also flips_{step}.txt / flip.txt in the same style (not files of the reference)."""
     with open(os.path.join(out_dir, f"psnrs_{step}.txt"), "w") as f:
         f.write(" ".join([str(v) for v in psnr_values]))
     with open(os.path.join(out_dir, f"ssims_{step}.txt"), "w") as f:
@@ -44,10 +46,16 @@ def write_metric_files(out_dir: str, step, psnr_values, ssim_values) -> None:
         f.write("{}".format(np.mean(np.array(psnr_values))))
     with open(os.path.join(out_dir, "ssim.txt"), "w") as f:
         f.write("{}".format(np.mean(np.array(ssim_values))))
+    if flip_values is not None:
+        with open(os.path.join(out_dir, f"flips_{step}.txt"), "w") as f:
+            f.write(" ".join([str(v) for v in flip_values]))
+        with open(os.path.join(out_dir, "flip.txt"), "w") as f:
+            f.write("{}".format(np.mean(np.array(flip_values))))
 
 
 def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192, normalize_disp: bool = False, out_dir: Optional[str] = None,
-             step=None, save_output: bool = False, render_path: bool = False) -> dict:
+             step=None, save_output: bool = False, render_path: bool = False, flip: bool = False,
+             flip_pixels_per_degree: Optional[float] = None) -> dict:
     """Render and score every view (eval.py:155-215).
 
     model / variables: what models.construct_nerf returns; views: batches as device_views yields them; rng: the render key (eval.py passes
@@ -55,7 +63,11 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
     {idx:03d}.png and disp_{idx:03d}.png into out_dir, and (unless render_path) the metric files of write_metric_files for `step`.
 
     -> {"psnrs", "ssims": per-view Python floats, "psnr", "ssim": their means (None without views or with render_path), "seconds": wall
-    time of the loop, "rays_per_sec": rendered rays over it (train.py:450-452)}."""
+    time of the loop, "rays_per_sec": rendered rays over it (train.py:450-452)}.
+
+    flip=True also scores each view with utils.compute_flip(pred_color, pixels, flip_pixels_per_degree) (None: compute_ldrflip's default;
+    utils.FLIP_PPD_SUMMARY is what metric/summary.py uses): the result gains "flips" and "flip", save_output also writes
+    flips_{step}.txt and flip.txt.  With flip=False the keys, the files and the launches are those of the loop without it."""
     if save_output:
         if out_dir is None:
             raise ValueError("evaluate: save_output needs out_dir")
@@ -64,7 +76,7 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
     def render_fn(key_0, key_1, rays, path=None):
         return model.apply(variables, key_0, key_1, rays, False, path=path)
 
-    psnr_values, ssim_values = [], []
+    psnr_values, ssim_values, flip_values = [], [], []
     num_rays = 0
     t0 = time.perf_counter()
     for idx, batch in enumerate(views):
@@ -73,9 +85,14 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
         if not render_path:
             psnr = utils.compute_psnr(((pred_color - batch["pixels"]) ** 2).mean())
             ssim = utils.compute_ssim(pred_color, batch["pixels"], max_val=1.0)
-            pair = torch.stack([psnr.to(torch.float32), ssim]).cpu()          # the one read-back of the view: 8 bytes
+            scores = [psnr.to(torch.float32), ssim]
+            if flip:
+                scores.append(utils.compute_flip(pred_color, batch["pixels"], flip_pixels_per_degree))
+            pair = torch.stack(scores).cpu()                                  # the one read-back of the view: 8 bytes (12 with flip)
             psnr_values.append(float(pair[0]))
             ssim_values.append(float(pair[1]))
+            if flip:
+                flip_values.append(float(pair[2]))
         if save_output:
             utils.save_img(pred_color, os.path.join(out_dir, "{:03d}.png".format(idx)))
             utils.save_img(pred_disp[..., 0], os.path.join(out_dir, "disp_{:03d}.png".format(idx)))
@@ -83,9 +100,13 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
         torch.cuda.synchronize(pred_color.device)
     seconds = time.perf_counter() - t0
     if save_output and not render_path:
-        write_metric_files(out_dir, step, psnr_values, ssim_values)
+        write_metric_files(out_dir, step, psnr_values, ssim_values, flip_values if flip else None)
     have = bool(psnr_values)
-    return {"psnrs": psnr_values, "ssims": ssim_values,
-            "psnr": float(np.mean(np.array(psnr_values))) if have else None,
-            "ssim": float(np.mean(np.array(ssim_values))) if have else None,
-            "seconds": seconds, "rays_per_sec": num_rays / seconds if seconds > 0 else 0.0}
+    res = {"psnrs": psnr_values, "ssims": ssim_values,
+           "psnr": float(np.mean(np.array(psnr_values))) if have else None,
+           "ssim": float(np.mean(np.array(ssim_values))) if have else None,
+           "seconds": seconds, "rays_per_sec": num_rays / seconds if seconds > 0 else 0.0}
+    if flip:
+        res["flips"] = flip_values
+        res["flip"] = float(np.mean(np.array(flip_values))) if flip_values else None
+    return res

@@ -659,3 +659,42 @@ def ssim(img0: torch.Tensor, img1: torch.Tensor, *, max_val: float, filter_size:
         check(lib.rnerf_ssim(ptr(a), ptr(b), n, H, W, Ch, fs, float(filter_sigma), float(max_val), float(k1), float(k2), ptr(out_map),
                              ptr(mean), ptr(ws), torch.cuda.current_stream(dev).cuda_stream), "rnerf_ssim")
     return out_map if return_map else mean
+
+
+_flip_workspaces: dict = {}       # (device index, stream) -> uint8 tensor: rnerf_flip's workspace, kept and grown between calls
+
+
+def flip(reference: torch.Tensor, test: torch.Tensor, *, pixels_per_degree: float, return_map: bool = False) -> torch.Tensor:
+    """compute_ldrflip (metric/flip/flip_api.py:439-495) on the device (rnerf_flip).  reference, test: float32 device tensors
+    [..., H, W, 3], sRGB in [0, 1].  -> the mean FLIP error of each image, shape [...] (0-dim for [H, W, 3]), or with return_map the
+    error map [..., H, W].  Issued on the current stream of the images' device; nothing is synchronised.  The workspace (14 filtered
+    planes) is kept per device and stream and reused by later calls that fit in it."""
+    if tuple(reference.shape) != tuple(test.shape):
+        raise ValueError(f"flip: the images differ in shape: {tuple(reference.shape)} vs {tuple(test.shape)}")
+    if reference.dim() < 3 or int(reference.shape[-1]) != 3:
+        raise ValueError(f"flip: need [..., H, W, 3] images, got shape {tuple(reference.shape)}")
+    if reference.device != test.device:
+        raise ValueError(f"flip: the images are on different devices ({reference.device}, {test.device})")
+    ppd = float(pixels_per_degree)
+    *lead, H, W, _ = (int(s) for s in reference.shape)
+    a, b = _chk(reference, "reference"), _chk(test, "test")
+    n = 1
+    for s in lead:
+        n *= s
+    dev = a.device
+    if n == 0 or H == 0 or W == 0:
+        return torch.empty(tuple(lead) + ((H, W) if return_map else ()), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nb = lib.rnerf_flip_workspace_bytes(n, H, W, ppd)
+        if nb == 0:
+            check(-1, "rnerf_flip_workspace_bytes")
+        key = (dev.index, stream)
+        ws = _flip_workspaces.get(key)
+        if ws is None or ws.numel() < nb:
+            ws = _flip_workspaces[key] = torch.empty(nb, dtype=torch.uint8, device=dev)
+        out_map = torch.empty(tuple(lead) + (H, W), dtype=torch.float32, device=dev) if return_map else None
+        mean = None if return_map else torch.empty(tuple(lead), dtype=torch.float32, device=dev)
+        check(lib.rnerf_flip(ptr(a), ptr(b), n, H, W, ppd, ptr(out_map), ptr(mean), ptr(ws), stream), "rnerf_flip")
+    return out_map if return_map else mean

@@ -1,6 +1,6 @@
 """Host-side mirror of the parts of rnerf/utils.py that sit on the boundary of the hot path.
 
-Rays / Stats / namedtuple_map / render_image / compute_psnr / compute_ssim (on the device) / save_img / learning_rate_decay /
+Rays / Stats / namedtuple_map / render_image / compute_psnr / compute_ssim / compute_flip (on the device) / save_img / learning_rate_decay /
 default flags.  The rest of the reference's utils.py (absl flags, gin, file-system wrappers) is out of scope.
 """
 from __future__ import annotations
@@ -103,6 +103,44 @@ def compute_ssim(img0, img1, max_val, filter_size=11, filter_sigma=1.5, k1=0.01,
     from . import ops
     a, b = as_f32(img0), as_f32(img1)
     return ops.ssim(a, b, max_val=max_val, filter_size=filter_size, filter_sigma=filter_sigma, k1=k1, k2=k2, return_map=return_map)
+
+
+FLIP_PPD_DEFAULT = (0.7 * 3840 / 0.7) * math.pi / 180      # compute_ldrflip's default (flip_api.py:439): a 0.7 m wide 4K monitor at 0.7 m
+FLIP_PPD_SUMMARY = 0.3 * (400 / 0.5) * math.pi / 180        # metric/summary.py:72-75
+
+
+def compute_flip(reference, test, pixels_per_degree=None, return_map=False):
+    """LDR-FLIP, compute_ldrflip (metric/flip/flip_api.py:439-495), on the device (ops.flip -> rnerf_flip).
+
+    reference, test: torch tensors or numpy arrays of one shape [..., H, W, 3] (channels last, sRGB in [0, 1]); a numpy (or CPU) argument
+    is uploaded to the device of the other argument, or to the current device.  pixels_per_degree: None is compute_ldrflip's default
+    (FLIP_PPD_DEFAULT); metric/summary.py scores with FLIP_PPD_SUMMARY.  Computed in fp32.  Returns a device tensor: each image's mean
+    error (shape [...], 0-dim for one image: summary.py:78) or, with return_map, the error map [..., H, W].  Nothing is synchronised.
+    There is no CPU fallback."""
+    s0, s1 = tuple(np.shape(reference)), tuple(np.shape(test))
+    if s0 != s1:
+        raise ValueError(f"compute_flip: the images differ in shape: {s0} vs {s1}")
+    if len(s0) < 3 or s0[-1] != 3:
+        raise ValueError(f"compute_flip: need [..., H, W, 3] images, got shape {s0}")
+    ppd = FLIP_PPD_DEFAULT if pixels_per_degree is None else float(pixels_per_degree)
+    if not (ppd > 0.0 and math.isfinite(ppd)):
+        raise ValueError(f"compute_flip: pixels_per_degree must be finite and > 0, got {pixels_per_degree}")
+
+    def on_device(t):
+        return isinstance(t, torch.Tensor) and t.is_cuda
+    if on_device(reference):
+        dev = reference.device
+    elif on_device(test):
+        dev = test.device
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device())
+
+    def as_f32(t):
+        if not isinstance(t, torch.Tensor):
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float32)))
+        return t.to(device=dev, dtype=torch.float32)
+    from . import ops
+    return ops.flip(as_f32(reference), as_f32(test), pixels_per_degree=ppd, return_map=return_map)
 
 
 def save_img(img, pth, to8b=True):
