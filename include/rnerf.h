@@ -37,8 +37,8 @@ extern "C" {
  * stream (rnerf_nerfmlp_packed_bytes grew) — and this round's additions: enum rnerf_backward gains F16X3_LO8, rnerf_sample_batch.
  * 4: the opt-in schedule fields no caller set are gone.  rnerf_train_cfg ends with aux_stream, grads_stream (nothing in between);
  * rnerf_prefetch ends with side_stream (the march always forks right before the last NerfMLP wgrad); rnerf_bkgd_backward is the only
- * background-MLP backward entry point.  Still 4 with rnerf_flip / rnerf_flip_workspace_bytes: they are appended, no existing entry
- * point or struct moved. */
+ * background-MLP backward entry point.  Still 4 with rnerf_flip / rnerf_flip_workspace_bytes and with rnerf_visual_hull_*: they are appended, no
+ * existing entry point or struct moved. */
 #define RNERF_VERSION 4
 
 enum rnerf_status {
@@ -574,6 +574,30 @@ int rnerf_ssim(const float* img0, const float* img1, int64_t n, int32_t H, int32
 size_t rnerf_flip_workspace_bytes(int64_t n, int32_t H, int32_t W, double pixels_per_degree);
 int rnerf_flip(const float* reference, const float* test, int64_t n, int32_t H, int32_t W, double pixels_per_degree, float* map,
                float* mean, void* workspace, void* stream);
+
+/* ---- Capture scenes: visual-hull carving.  Replaces calib/make_visual_hull.py:107-146 (the voxel grid, the projection loop over the
+ * views with project_2d :30-44, and the values of mesh.pkl), every step in float64 as there.  Appended; RNERF_VERSION stays 4.
+ * masks: uint8[V][H][W], > 0 = object (cv2.imread(mask)[..., 0] > 0, :126,132); pv: double[V][12], the row-major 3 x 4 matrix
+ * [cam_mat | 0] @ to_view_matrix(T) of each view (:40,92-93; formed on the host); g: the voxel grid, centres
+ * linspace(0, 1, G)[i] * (nmax - nmin) + nmin (:112-120), count / out indexed [x][y][z], x slowest; g->layout is not read.
+ * Per voxel and view: (a, b, c) = pv @ (x, y, z, 1), u = a / c, v = b / c, pixel (clip(round_half_even(v), 0, H - 1),
+ * clip(round_half_even(u), 0, W - 1)) (:129-130); count = the number of views whose mask is set there.  No test of the sign of c, as in
+ * the reference.  Where the reference is unspecified (c == 0, a NaN) the pixel clamps into the image: NaN -> 0, +-inf -> the edge.
+ * Counts are integers kept in registers and stored once: no atomics, the same result on every run.
+ * Limits (RNERF_ERR_ARG otherwise; checked before any device work): cubic grids, 2 <= G, G^3 < 2^31; 1 <= V < 2^31; H, W >= 1 and
+ * H * W < 2^31.
+ *   rnerf_visual_hull_workspace_bytes: 4 V H ceil(W / 32) — the masks packed to one bit per pixel (0 with a message for a bad size).
+ *   rnerf_visual_hull_pack: fills `workspace` (4-byte aligned) from `masks`.
+ *   rnerf_visual_hull_count: packs `masks` into `workspace` (masks == NULL: the workspace already holds the bits of these V views), then
+ *     count = (accumulate ? count : 0) + views inside; accumulate (0 / 1) lets a host with hundreds of large masks upload them in chunks.
+ *   rnerf_visual_hull_finalize: out = (count / total_views > threshold) ? ior_inside : ior_outside, the comparison in float64 (:136,141;
+ *     the reference's values are 1.33 and 1.0). */
+size_t rnerf_visual_hull_workspace_bytes(int64_t num_views, int32_t height, int32_t width);
+int rnerf_visual_hull_pack(const uint8_t* masks, int64_t num_views, int32_t height, int32_t width, void* workspace, void* stream);
+int rnerf_visual_hull_count(const uint8_t* masks, int64_t num_views, int32_t height, int32_t width, const double* pv, const rnerf_grid* g,
+                            int32_t accumulate, int32_t* count, void* workspace, void* stream);
+int rnerf_visual_hull_finalize(const int32_t* count, const rnerf_grid* g, int64_t total_views, double threshold, double ior_inside,
+                               double ior_outside, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -159,6 +159,11 @@ SIGNATURES = {
     "rnerf_ssim": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp]),
     "rnerf_flip_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32, _dbl]),
     "rnerf_flip": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _dbl, _vp, _vp, _vp, _vp]),
+    # capture scenes (csrc/hull.hip)
+    "rnerf_visual_hull_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32]),
+    "rnerf_visual_hull_pack": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    "rnerf_visual_hull_count": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _GP, _i32, _vp, _vp, _vp]),
+    "rnerf_visual_hull_finalize": (C.c_int, [_vp, _GP, _i64, _dbl, _dbl, _dbl, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
