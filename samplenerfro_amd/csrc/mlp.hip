@@ -1647,8 +1647,6 @@ template <int KT, int NT> struct WgTrShape {
   static_assert(WK * TK == KT && WN * TN == NTR && WK * WN <= 8 && (!EXTRA || (TK == 2 && WN == 2)), "tile split");
 };
 constexpr int WGTR_NCH = 2;      // n-tiles of B fragments fetched at a time when the A side is resident
-template <int NP> constexpr int wgtr_nbuf() { return NP == 2 ? 4 : 8; }       // ring depth: what fits 160 KiB
-template <int NP> constexpr int wgtr_lds_bytes() { return wgtr_nbuf<NP>() * ((10 + 8) * NP + 1) * 1024; }       // largest job: 10 k-tiles + 8 n-tiles
 
 __device__ __forceinline__ half8 tr_read8(const char* p) {      // rows k .. k+3 at p, rows k+4 .. k+7 at p + 256 (4 rows x 64 B)
   typedef short short4v __attribute__((ext_vector_type(4)));
@@ -1665,55 +1663,170 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
 }
 
 struct WgTrSegs { int qx, KTa, qx2, qd, NTa, KSd, qd2, KSd2; };    // slot bases / extents of the (up to two) X and dY segments of a job
+// the slot pair (block parity a = 0 / 1) of X k-tile t / of dY n-tile nt
+__device__ __forceinline__ void x_slots(const WgTrSegs& sg, int t, int& s0, int& s1) {
+  s0 = t < sg.KTa ? sg.qx + 2 * t : sg.qx2 + 2 * (t - sg.KTa);
+  s1 = s0 + 1;
+}
+__device__ __forceinline__ void d_slots(const WgTrSegs& sg, int nt, int& s0, int& s1) {
+  const int rel = nt < sg.NTa ? 2 * nt : 2 * (nt - sg.NTa);
+  const int qb = nt < sg.NTa ? sg.qd : sg.qd2, ks = nt < sg.NTa ? sg.KSd : sg.KSd2;
+  s0 = qb + (rel < ks ? rel : ks - 1);      // a slot beyond the segment's k-steps repeats its last one: those columns are dropped by the reduction
+  s1 = qb + (rel + 1 < ks ? rel + 1 : ks - 1);
+}
 
-template <int NP, int KT, int NT>
+// One DMA instruction's source, per ring step: (wave-uniform base of its slot pair and plane, advanced by a uniform stride per 32-row tile
+// and per 16-row half of it: SGPRs) + (lane part: one 32-bit VGPR per block)
+struct WgTrDma { const char* sbase; unsigned voff, tstride, hstride; };
+// lane part of every 16-bit transpose-read address: row (8 kh + (i >> 2)) * 64 + slot parity a * 32 + (i & 3) * 8, i = lane & 15
+__device__ __forceinline__ unsigned wgtr_lane_off(int lane) {
+  return (unsigned)((8 * (lane >> 5) + ((lane & 15) >> 2)) * 64 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8);
+}
+constexpr int wgtr_step_bytes(int nblk) { return (nblk + 1) * 1024; }      // the blocks of a ring step + the row-scale block (64 B used)
+
+// ---- what differs between the operand formats of the transposing wgrad: the blocks of a ring step and how fragments come out of them ------
+// A policy names the planes (LO: lo planes beside the hi ones; NPLANES: dY planes ahead of the row scales), the ring (NBUF steps of
+// nblk(KT, NT) blocks; lds_bytes() for the largest job: 10 k-tiles + 8 n-tiles), what the DMA instruction of block b fetches (dma) and
+// from where at local step sc of 32-row tile t32 (step_src), and the fragment reads out of the ring slot at ring0 (Frags: read_a gives
+// k-tile t of X times the row scales, read_b n-tile nt of dY; the hi part, and the lo part where LO).
+// f16 planes (RNERF_BWD_F16: NP = 1, RNERF_BWD_F16X2: NP = 2): block (NP t + part) is plane `part` of tile t
+template <int NP> struct F16Planes {
+  static constexpr bool LO = NP == 2;
+  static constexpr int NPLANES = NP;
+  static constexpr int NBUF = NP == 2 ? 4 : 8;       // ring depth: what fits 160 KiB
+  static constexpr int nblk(int KT, int NT) { return (KT + NT) * NP; }
+  static constexpr int lds_bytes() { return NBUF * wgtr_step_bytes(nblk(10, 8)); }
+  template <int KT, int NT>
+  static __device__ __forceinline__ WgTrDma dma(int b, int lane, const uint4* __restrict__ saved, const uint4* __restrict__ dy, long long R, const WgTrSegs& sg) {
+    // lane L = 4 r + 2 a + h fetches the 16 B (slot a of the pair, row r, half h)
+    const int r = lane >> 2, a = (lane >> 1) & 1, h = lane & 1;
+    const int t = b / NP, part = b % NP;
+    int slot0, slot1;
+    const uint4* base;
+    WgTrDma d;
+    if (t < KT) {
+      x_slots(sg, t, slot0, slot1);
+      base = saved + (part ? sv_lo0(R) : 0);
+      d.tstride = (unsigned)(SAVE_SLOTS * 64 * sizeof(uint4));
+    } else {
+      d_slots(sg, t - KT, slot0, slot1);
+      base = dy + (part ? dy_plane_uint4(R, 1) : 0);
+      d.tstride = (unsigned)(DY_SLOTS * 64 * sizeof(uint4));
+    }
+    static_assert(sv_addr(1, 0, 0, 0) == dy_addr(1, 0, 0, 0) && sv_addr(0, 0, 1, 1) == dy_addr(0, 0, 1, 1), "one lane-offset formula for both tensors");
+    d.sbase = (const char*)(base + sv_addr(__builtin_amdgcn_readfirstlane(slot0), 0, 0, 0));
+    d.voff = (unsigned)((sv_addr(a ? __builtin_amdgcn_readfirstlane(slot1 - slot0) : 0, 0, r, h)) * sizeof(uint4));
+    d.hstride = 0;      // one constant for every f16 block: in step_src
+    return d;
+  }
+  static __device__ __forceinline__ const char* step_src(const WgTrDma& d, size_t t32, int sc) {
+    return d.sbase + t32 * d.tstride + (sc & 1) * (32 * sizeof(uint4));
+  }
+  template <int KT, int NT> struct Frags {
+    const char* ring;
+    __device__ __forceinline__ Frags(const char* ring0, int lane) : ring(ring0 + wgtr_lane_off(lane)) {}
+    __device__ __forceinline__ void read_a(int t, const half8& sc8, half8& h, half8& l) const {
+      const char* p = ring + t * NP * 1024;
+      h = tr_read8(p) * sc8;
+      if constexpr (LO) l = tr_read8(p + 1024) * sc8;
+    }
+    __device__ __forceinline__ void read_b(int nt, half8& h, half8& l) const {
+      const char* p = ring + (KT + nt) * NP * 1024;
+      h = tr_read8(p);
+      if constexpr (LO) l = tr_read8(p + 1024);
+    }
+  };
+};
+
+// RNERF_BWD_F16X3_LO8: f16 hi planes as above (block t = tile t), the lo planes as e4m3 bytes behind them.
+// A lo tile of a 16-row step is 512 B in LDS, [row r][slot parity a][16 B = half 0 | half 1]; ONE DMA instruction builds TWO of them (lane
+// L: tile L >> 5, row (L & 31) >> 1, parity L & 1 — 16 B = both halves of (slot, row), contiguous in the lo8 plane).  The 8-bit transpose
+// read ds_read_b64_tr_b8 (within a 16-lane group destination lane i, byte j receives byte i & 7 of the 8 bytes addressed by source lane
+// 2 j + (i >> 3): tools/ubench/tr8_cvt_probe.hip) hands lane (m = 16 a + i, kh) the 8 rows 8 kh .. 8 kh + 7 of feature position m in ONE
+// read; four v_cvt_scalef32_pk_f16_fp8 turn them into the f16 lo fragment, and the three f16 MFMAs per product are those of the f16 lo
+// planes — with the exact f16 hi parts in both cross terms.  Per step: (KT + NT) KiB of hi + (KT + NT) / 2 KiB of lo blocks.
+__device__ __forceinline__ int2v tr_read8b(const char* p) {
+  typedef __attribute__((address_space(3))) int2v lds_int2;
+  return __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_int2*)p);
+}
+struct Lo8Planes {
+  static constexpr bool LO = true;
+  static constexpr int NPLANES = 2;
+  static constexpr int NBUF = 4;      // ring depth (5 for the smaller steps measured slower: DESIGN.md section 3.3)
+  static constexpr int nblk(int KT, int NT) { return KT + NT + (KT + 1) / 2 + (NT + 1) / 2; }
+  static constexpr int lds_bytes() { return NBUF * wgtr_step_bytes(nblk(10, 8)); }
+  template <int KT, int NT>
+  static __device__ __forceinline__ WgTrDma dma(int b, int lane, const uint4* __restrict__ saved, const uint4* __restrict__ dy, long long R, const WgTrSegs& sg) {
+    constexpr int NHI = KT + NT, NLX = (KT + 1) / 2;
+    WgTrDma d;
+    if (b < NHI) {                      // f16 hi block of tile b: as in F16Planes<1>
+      const int r = lane >> 2, a = (lane >> 1) & 1, h = lane & 1;
+      int s0, s1;
+      const bool is_x = b < KT;
+      if (is_x) x_slots(sg, b, s0, s1); else d_slots(sg, b - KT, s0, s1);
+      d.sbase = (const char*)((is_x ? saved : dy) + sv_addr(__builtin_amdgcn_readfirstlane(s0), 0, 0, 0));
+      d.voff = (unsigned)((sv_addr(a ? __builtin_amdgcn_readfirstlane(s1 - s0) : 0, 0, r, h)) * sizeof(uint4));
+      d.tstride = (unsigned)((is_x ? SAVE_SLOTS : DY_SLOTS) * 64 * sizeof(uint4));
+      d.hstride = (unsigned)(32 * sizeof(uint4));
+      return d;
+    }
+    // e4m3 lo block: two tiles, lane = 32 (tile parity) + 2 r + a, 16 B = (slot a, row r, both halves)
+    const int lb = b - NHI;
+    const bool is_x = lb < NLX;
+    const int t0 = 2 * (is_x ? lb : lb - NLX) + (lane >> 5);
+    const int r = (lane & 31) >> 1, a = lane & 1;
+    int s0, s1;
+    if (is_x) x_slots(sg, t0 < KT ? t0 : KT - 1, s0, s1); else d_slots(sg, t0 < NT ? t0 : NT - 1, s0, s1);
+    d.sbase = is_x ? (const char*)(saved + sv_lo0(R)) : (const char*)(dy + dy_plane_uint4(R, 1));
+    d.voff = (unsigned)(((a ? s1 : s0) * 32 + r) * 16);
+    d.tstride = (unsigned)((is_x ? SAVE_SLOTS : DY_SLOTS) * 32 * 16);
+    d.hstride = 16u * 16u;
+    return d;
+  }
+  static __device__ __forceinline__ const char* step_src(const WgTrDma& d, size_t t32, int sc) {
+    return d.sbase + t32 * d.tstride + (sc & 1) * d.hstride;
+  }
+  template <int KT, int NT> struct Frags {
+    static constexpr int LOX = (KT + NT) * 1024, LOD = LOX + (KT + 1) / 2 * 1024;      // the lo tiles of X / of dY
+    const char *ring, *ring8;
+    // lo tile: row (8 kh + (i >> 1)) * 32 + slot parity a * 16 + (i & 1) * 8, i = lane & 15
+    __device__ __forceinline__ Frags(const char* ring0, int lane)
+        : ring(ring0 + wgtr_lane_off(lane)), ring8(ring0 + (unsigned)((8 * (lane >> 5) + ((lane & 15) >> 1)) * 32 + ((lane >> 4) & 1) * 16 + (lane & 1) * 8)) {}
+    __device__ __forceinline__ void read_a(int t, const half8& sc8, half8& h, half8& l) const {
+      h = tr_read8(ring + t * 1024) * sc8;
+      l = lo8_decode(tr_read8b(ring8 + LOX + t * 512), LO8_SCALE_X) * sc8;
+    }
+    __device__ __forceinline__ void read_b(int nt, half8& h, half8& l) const {
+      h = tr_read8(ring + (KT + nt) * 1024);
+      l = lo8_decode(tr_read8b(ring8 + LOD + nt * 512), LO8_SCALE_D);
+    }
+  };
+};
+
+template <class Planes, int KT, int NT>
 __device__ __forceinline__ void wgrad_body_tr(const uint4* __restrict__ saved, const uint4* __restrict__ dy, long long R, float* __restrict__ pg,
                                                float* __restrict__ pbias, const WgTrSegs sg, int g, int G, char* smem) {
   using SH = WgTrShape<KT, NT>;
   constexpr int TK = SH::TK, TN = SH::TN;
-  constexpr int NBLK = (KT + NT) * NP, NDMA = (NBLK + 7) / 8, STEP_BYTES = (NBLK + 1) * 1024;   // + the row-scale block (64 B used)
-  constexpr int WGTR_NBUF = wgtr_nbuf<NP>(), AHEAD = WGTR_NBUF - 1;
+  constexpr int NBLK = Planes::nblk(KT, NT), NDMA = (NBLK + 7) / 8, STEP_BYTES = wgtr_step_bytes(NBLK);
+  constexpr int WGTR_NBUF = Planes::NBUF, AHEAD = WGTR_NBUF - 1;
+  static_assert((WGTR_NBUF & (WGTR_NBUF - 1)) == 0, "ring slots are addressed with a mask");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wk = wave / SH::WN, wn = wave % SH::WN;
   const bool active = wave < SH::WK * SH::WN;
-  const float* __restrict__ rs = (const float*)(dy + dy_plane_uint4(R, NP));
+  const float* __restrict__ rs = (const float*)(dy + dy_plane_uint4(R, Planes::NPLANES));
   const float mref = rs[R];                                     // written by the dgrad's atomicMax
   const float inv_mref = mref > 0.f ? 1.0f / mref : 0.f;        // m_ref is a power of two: exact
-  // DMA roles: block b = wave + 8 i (clamped: a surplus instruction re-fetches the last block, same bytes to the same place).  The
-  // source address of a block is (wave-uniform base of its slot pair and part, advanced by a uniform stride per 32-row tile: SGPRs) +
-  // (lane part: row r, slot parity a, half h: one 32-bit VGPR per block)
-  const char* sbase[NDMA];
-  unsigned tstride[NDMA], voff[NDMA];
+  // DMA roles: block b = wave + 8 i (clamped: a surplus instruction re-fetches the last block, same bytes to the same place)
+  WgTrDma blk[NDMA];
   unsigned lds_blk[NDMA];
-  {
-    const int r = lane >> 2, a = (lane >> 1) & 1, h = lane & 1;
 #pragma unroll
-    for (int i = 0; i < NDMA; ++i) {
-      int b = wave + 8 * i;
-      b = b < NBLK ? b : NBLK - 1;
-      const int t = b / NP, part = b % NP;
-      int slot0, slot1;              // the slots lane parity a = 0 / 1 fetch
-      const uint4* base;
-      if (t < KT) {
-        slot0 = t < sg.KTa ? sg.qx + 2 * t : sg.qx2 + 2 * (t - sg.KTa);
-        slot1 = slot0 + 1;
-        base = saved + (part ? sv_lo0(R) : 0);
-        tstride[i] = (unsigned)(SAVE_SLOTS * 64 * sizeof(uint4));
-      } else {     // a slot beyond the segment's k-steps repeats its last one: those columns are dropped by the reduction
-        const int nt = t - KT;
-        const int rel = nt < sg.NTa ? 2 * nt : 2 * (nt - sg.NTa);
-        const int qb = nt < sg.NTa ? sg.qd : sg.qd2, ks = nt < sg.NTa ? sg.KSd : sg.KSd2;
-        slot0 = qb + (rel < ks ? rel : ks - 1);
-        slot1 = qb + (rel + 1 < ks ? rel + 1 : ks - 1);
-        base = dy + (part ? dy_plane_uint4(R, 1) : 0);
-        tstride[i] = (unsigned)(DY_SLOTS * 64 * sizeof(uint4));
-      }
-      static_assert(sv_addr(1, 0, 0, 0) == dy_addr(1, 0, 0, 0) && sv_addr(0, 0, 1, 1) == dy_addr(0, 0, 1, 1), "one lane-offset formula for both tensors");
-      sbase[i] = (const char*)(base + sv_addr(__builtin_amdgcn_readfirstlane(slot0), 0, 0, 0));
-      voff[i] = (unsigned)((sv_addr(a ? __builtin_amdgcn_readfirstlane(slot1 - slot0) : 0, 0, r, h)) * sizeof(uint4));
-      lds_blk[i] = (unsigned)b * 1024u;
-    }
+  for (int i = 0; i < NDMA; ++i) {
+    int b = wave + 8 * i;
+    b = b < NBLK ? b : NBLK - 1;
+    blk[i] = Planes::template dma<KT, NT>(b, lane, saved, dy, R, sg);
+    lds_blk[i] = (unsigned)b * 1024u;
   }
   // the 16 row scales of a step ride the same ring (every VMEM operation of the loop is a DMA: one counter discipline): wave 0 fetches
   // them as one more DMA instruction, lanes 0..3 carry 4 floats each (the other lanes repeat them)
@@ -1721,13 +1834,13 @@ __device__ __forceinline__ void wgrad_body_tr(const uint4* __restrict__ saved, c
   const long long n_t32 = R / 32;
   const int my_tiles = g < n_t32 ? (int)((n_t32 - 1 - g) / G) + 1 : 0;
   const int n_steps = 2 * my_tiles;
-  auto issue = [&](int s) {                                     // DMA of local step s into ring slot s & 3 (steps past the end: the last one again)
+  auto issue = [&](int s) {                                     // DMA of local step s into ring slot s & (WGTR_NBUF - 1) (steps past the end: the last one again)
     const int sc = s < n_steps ? s : n_steps - 1;
     const size_t t32 = (size_t)g + (size_t)(sc >> 1) * G;
     const unsigned ring = (unsigned)(s & (WGTR_NBUF - 1)) * STEP_BYTES;
 #pragma unroll
     for (int i = 0; i < NDMA; ++i)
-      glds16_nt_s(sbase[i] + t32 * tstride[i] + (sc & 1) * (32 * sizeof(uint4)), voff[i], __builtin_amdgcn_readfirstlane(ring + lds_blk[i]));
+      glds16_nt_s(Planes::step_src(blk[i], t32, sc), blk[i].voff, __builtin_amdgcn_readfirstlane(ring + lds_blk[i]));
     if (wave == 0) glds16_nt((const char*)(rs_src + t32 * 32 + (sc & 1) * 16), __builtin_amdgcn_readfirstlane(ring + NBLK * 1024u));
   };
   const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1740,8 +1853,6 @@ __device__ __forceinline__ void wgrad_body_tr(const uint4* __restrict__ saved, c
   if (n_steps > 0) {
 #pragma unroll
     for (int s = 0; s < AHEAD; ++s) issue(s);
-    // lane part of every transpose-read address: row (8 kh + (i >> 2)) * 64 + slot parity a * 32 + (i & 3) * 8, i = lane & 15
-    const unsigned lane_off = (unsigned)((8 * (lane >> 5) + ((lane & 15) >> 2)) * 64 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8);
     const int kh = lane >> 5;
     for (int s = 0; s < n_steps; ++s) {
       if (wave == 0) wait_vmcnt<(AHEAD - 1) * (NDMA + 1)>(); else
@@ -1754,36 +1865,23 @@ __device__ __forceinline__ void wgrad_body_tr(const uint4* __restrict__ saved, c
       issue(s + AHEAD);
       if (active) {
         const char* ring0 = smem + (s & (WGTR_NBUF - 1)) * STEP_BYTES;
-        const char* ring = ring0 + lane_off;
+        const typename Planes::template Frags<KT, NT> frags(ring0, lane);
         const float4 s0 = *(const float4*)(ring0 + NBLK * 1024 + kh * 32), s1 = *(const float4*)(ring0 + NBLK * 1024 + kh * 32 + 16);
         const half8 sc8 = {(_Float16)(s0.x * inv_mref), (_Float16)(s0.y * inv_mref), (_Float16)(s0.z * inv_mref), (_Float16)(s0.w * inv_mref),
                            (_Float16)(s1.x * inv_mref), (_Float16)(s1.y * inv_mref), (_Float16)(s1.z * inv_mref), (_Float16)(s1.w * inv_mref)};
         // Operands are fetched and consumed in chunks so that the live set beside the TK x TN accumulators stays small enough for
         // WGRAD_VGPRS without spilling: the smaller operand side stays resident for the step, the other side streams through in
         // chunks (A fragments one k-tile at a time when TK > TN, else B fragments NCH n-tiles at a time).
-        half8 beh, bel;
-        if constexpr (SH::EXTRA) {
-          const char* p = ring + (KT + NT - 1) * NP * 1024;
-          beh = tr_read8(p);
-          if constexpr (NP == 2) bel = tr_read8(p + 1024);
-        }
+        half8 beh, bel;                     // the B fragments of the extra tile's n-tile
+        if constexpr (SH::EXTRA) frags.read_b(NT - 1, beh, bel);
         static_assert(SH::WK >= TN, "bias owners");
-        auto read_a = [&](int i, half8& h, half8& l) {
-          const char* p = ring + (wk * TK + i) * NP * 1024;
-          h = tr_read8(p) * sc8;
-          if constexpr (NP == 2) l = tr_read8(p + 1024) * sc8;
-        };
-        auto read_b = [&](int j, half8& h, half8& l) {
-          const char* p = ring + (KT + wn * TN + j) * NP * 1024;
-          h = tr_read8(p);
-          if constexpr (NP == 2) l = tr_read8(p + 1024);
-        };
+        auto read_a = [&](int i, half8& h, half8& l) { frags.read_a(wk * TK + i, sc8, h, l); };
+        auto read_b = [&](int j, half8& h, half8& l) { frags.read_b(wn * TN + j, h, l); };
         // bias row: wave (wk, wn) owns it for n-tile wn TN + wk, wk < TN (the 9th n-tile of the Dense_9 + sigma job has no owner: the
         // sigma bias comes out of the rgb-head job, which reads the same head-gradient slot).  A B fragment holds, per lane, 8 rows of one
         // column and sc8 the scales of the same 8 rows: four v_dot2_f32_f16 per fragment instead of an MFMA with a one-row A operand and
         // a 16-register accumulator (the kernel has to stay within WGRAD_VGPRS).
         auto dot8 = [&](const half8& x, float c) -> float {
-          typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 #pragma unroll
           for (int k = 0; k < 4; ++k) c = __builtin_amdgcn_fdot2(half2v{sc8[2 * k], sc8[2 * k + 1]}, half2v{x[2 * k], x[2 * k + 1]}, c, false);
           return c;
@@ -1791,7 +1889,7 @@ __device__ __forceinline__ void wgrad_body_tr(const uint4* __restrict__ saved, c
         auto bias_row = [&](int j, const half8& h, const half8& l) {
           if (wk == j) {
             accb = dot8(h, accb);
-            if constexpr (NP == 2) accb = dot8(l, accb);
+            if constexpr (Planes::LO) accb = dot8(l, accb);
           }
         };
         half8 ae_h, ae_l;                   // the A fragments of the extra tile's k-tile (EXTRA: TK == 2, A side resident)
@@ -1807,7 +1905,7 @@ __device__ __forceinline__ void wgrad_body_tr(const uint4* __restrict__ saved, c
             if (i + 1 < TK) read_a(i + 1, an_h, an_l);         // the next k-tile's fragments are on their way while this one's MFMAs issue
 #pragma unroll
             for (int j = 0; j < TN; ++j) acc[i][j] = mfma_h8(ah, bh[j], acc[i][j]);
-            if constexpr (NP == 2) {
+            if constexpr (Planes::LO) {
 #pragma unroll
               for (int j = 0; j < TN; ++j) acc[i][j] = mfma_h8(ah, bl[j], acc[i][j]);
 #pragma unroll
@@ -1831,7 +1929,7 @@ __device__ __forceinline__ void wgrad_body_tr(const uint4* __restrict__ saved, c
             for (int i = 0; i < TK; ++i)
 #pragma unroll
               for (int jj = 0; jj < NCH; ++jj) acc[i][c * NCH + jj] = mfma_h8(ah[i], bh[jj], acc[i][c * NCH + jj]);
-            if constexpr (NP == 2) {
+            if constexpr (Planes::LO) {
 #pragma unroll
               for (int i = 0; i < TK; ++i)
 #pragma unroll
@@ -1844,12 +1942,12 @@ __device__ __forceinline__ void wgrad_body_tr(const uint4* __restrict__ saved, c
 #pragma unroll
             for (int jj = 0; jj < NCH; ++jj) bias_row(c * NCH + jj, bh[jj], bl[jj]);
           }
-          if constexpr (SH::EXTRA) { ae_h = wn ? ah[1] : ah[0]; if constexpr (NP == 2) ae_l = wn ? al[1] : al[0]; }
+          if constexpr (SH::EXTRA) { ae_h = wn ? ah[1] : ah[0]; if constexpr (Planes::LO) ae_l = wn ? al[1] : al[0]; }
         }
         if constexpr (SH::EXTRA) {          // wn picks which of the wave's two k-tiles (a select on registers, no branch)
           static_assert(!SH::EXTRA || TK <= TN, "the extra tile reads the resident A fragments");
           acce = mfma_h8(ae_h, beh, acce);
-          if constexpr (NP == 2) {
+          if constexpr (Planes::LO) {
             acce = mfma_h8(ae_h, bel, acce);
             acce = mfma_h8(ae_l, beh, acce);
           }
@@ -1882,227 +1980,11 @@ __device__ __forceinline__ void wgrad_body_tr(const uint4* __restrict__ saved, c
   }
 }
 
-// ---- the same body for RNERF_BWD_F16X3_LO8: f16 hi planes as above, the lo planes as e4m3 bytes -------------------------------------------
-// A lo tile of a 16-row step is 512 B in LDS, [row r][slot parity a][16 B = half 0 | half 1]; ONE DMA instruction builds TWO of them (lane
-// L: tile L >> 5, row (L & 31) >> 1, parity L & 1 — 16 B = both halves of (slot, row), contiguous in the lo8 plane).  The 8-bit transpose
-// read ds_read_b64_tr_b8 (within a 16-lane group destination lane i, byte j receives byte i & 7 of the 8 bytes addressed by source lane
-// 2 j + (i >> 3): tools/ubench/tr8_cvt_probe.hip) hands lane (m = 16 a + i, kh) the 8 rows 8 kh .. 8 kh + 7 of feature position m in ONE
-// read; four v_cvt_scalef32_pk_f16_fp8 turn them into the f16 lo fragment, and the three f16 MFMAs per product are those of the f16 lo
-// planes — with the exact f16 hi parts in both cross terms.  Per step: (KT + NT) KiB of hi + (KT + NT) / 2 KiB of lo blocks.
-template <int KT, int NT> struct WgTr8 {
-  static constexpr int NHI = KT + NT, NLX = (KT + 1) / 2, NLD = (NT + 1) / 2;
-  static constexpr int NBLK = NHI + NLX + NLD, NDMA = (NBLK + 7) / 8, STEP_BYTES = (NBLK + 1) * 1024;
-  static constexpr int LOX = NHI * 1024, LOD = (NHI + NLX) * 1024, SCALES = NBLK * 1024;
-};
-constexpr int WGTR8_NBUF = 4;      // ring depth (5 for the smaller steps measured slower: DESIGN.md section 3.3)
-constexpr int wgtr8_lds_bytes() { return WGTR8_NBUF * WgTr8<10, 8>::STEP_BYTES; }      // largest job: 10 k-tiles + 8 n-tiles
-__device__ __forceinline__ int2v tr_read8b(const char* p) {
-  typedef __attribute__((address_space(3))) int2v lds_int2;
-  return __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_int2*)p);
-}
-
-template <int KT, int NT>
-__device__ __forceinline__ void wgrad_body_tr8(const uint4* __restrict__ saved, const uint4* __restrict__ dy, long long R, float* __restrict__ pg,
-                                                float* __restrict__ pbias, const WgTrSegs sg, int g, int G, char* smem) {
-  using SH = WgTrShape<KT, NT>;
-  using L8 = WgTr8<KT, NT>;
-  constexpr int TK = SH::TK, TN = SH::TN;
-  constexpr int NHI = L8::NHI, NBLK = L8::NBLK, NDMA = L8::NDMA, STEP_BYTES = L8::STEP_BYTES;
-  constexpr int WGTR_NBUF = WGTR8_NBUF, AHEAD = WGTR_NBUF - 1;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wk = wave / SH::WN, wn = wave % SH::WN;
-  const bool active = wave < SH::WK * SH::WN;
-  const float* __restrict__ rs = (const float*)(dy + dy_plane_uint4(R, 2));
-  const float mref = rs[R];
-  const float inv_mref = mref > 0.f ? 1.0f / mref : 0.f;
-  // slot pair of X tile t / dY tile nt (see wgrad_body_tr)
-  auto x_slots = [&](int t, int& s0, int& s1) { s0 = t < sg.KTa ? sg.qx + 2 * t : sg.qx2 + 2 * (t - sg.KTa); s1 = s0 + 1; };
-  auto d_slots = [&](int nt, int& s0, int& s1) {
-    const int rel = nt < sg.NTa ? 2 * nt : 2 * (nt - sg.NTa);
-    const int qb = nt < sg.NTa ? sg.qd : sg.qd2, ks = nt < sg.NTa ? sg.KSd : sg.KSd2;
-    s0 = qb + (rel < ks ? rel : ks - 1);
-    s1 = qb + (rel + 1 < ks ? rel + 1 : ks - 1);
-  };
-  const char* sbase[NDMA];
-  unsigned tstride[NDMA], hstride[NDMA], voff[NDMA], lds_blk[NDMA];
-#pragma unroll
-  for (int i = 0; i < NDMA; ++i) {
-    int b = wave + 8 * i;
-    b = b < NBLK ? b : NBLK - 1;
-    lds_blk[i] = (unsigned)b * 1024u;
-    if (b < NHI) {                      // f16 hi block of tile b: lane = 4 r + 2 a + h, 16 B = (slot a, row r, half h)
-      const int r = lane >> 2, a = (lane >> 1) & 1, h = lane & 1;
-      int s0, s1;
-      const bool is_x = b < KT;
-      if (is_x) x_slots(b, s0, s1); else d_slots(b - KT, s0, s1);
-      sbase[i] = (const char*)((is_x ? saved : dy) + sv_addr(__builtin_amdgcn_readfirstlane(s0), 0, 0, 0));
-      voff[i] = (unsigned)((sv_addr(a ? __builtin_amdgcn_readfirstlane(s1 - s0) : 0, 0, r, h)) * sizeof(uint4));
-      tstride[i] = (unsigned)((is_x ? SAVE_SLOTS : DY_SLOTS) * 64 * sizeof(uint4));
-      hstride[i] = (unsigned)(32 * sizeof(uint4));
-    } else {                            // e4m3 lo block: two tiles, lane = 32 (tile parity) + 2 r + a, 16 B = (slot a, row r, both halves)
-      const int lb = b - NHI;
-      const bool is_x = lb < L8::NLX;
-      const int t0 = 2 * (is_x ? lb : lb - L8::NLX) + (lane >> 5);
-      const int r = (lane & 31) >> 1, a = lane & 1;
-      int s0, s1;
-      if (is_x) x_slots(t0 < KT ? t0 : KT - 1, s0, s1); else d_slots(t0 < NT ? t0 : NT - 1, s0, s1);
-      sbase[i] = is_x ? (const char*)(saved + sv_lo0(R)) : (const char*)(dy + dy_plane_uint4(R, 1));
-      voff[i] = (unsigned)(((a ? s1 : s0) * 32 + r) * 16);
-      tstride[i] = (unsigned)((is_x ? SAVE_SLOTS : DY_SLOTS) * 32 * 16);
-      hstride[i] = 16u * 16u;
-    }
-  }
-  const float* rs_src = rs + 4 * (lane & 3);
-  const long long n_t32 = R / 32;
-  const int my_tiles = g < n_t32 ? (int)((n_t32 - 1 - g) / G) + 1 : 0;
-  const int n_steps = 2 * my_tiles;
-  auto issue = [&](int s) {
-    const int sc = s < n_steps ? s : n_steps - 1;
-    const size_t t32 = (size_t)g + (size_t)(sc >> 1) * G;
-    const unsigned ring = (unsigned)(s % WGTR_NBUF) * STEP_BYTES;
-#pragma unroll
-    for (int i = 0; i < NDMA; ++i)
-      glds16_nt_s(sbase[i] + t32 * tstride[i] + (sc & 1) * hstride[i], voff[i], __builtin_amdgcn_readfirstlane(ring + lds_blk[i]));
-    if (wave == 0) glds16_nt((const char*)(rs_src + t32 * 32 + (sc & 1) * 16), __builtin_amdgcn_readfirstlane(ring + L8::SCALES));
-  };
-  const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  f32x16 acc[TK][TN], acce = zero;
-  float accb = 0.f;
-#pragma unroll
-  for (int i = 0; i < TK; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = zero;
-  if (n_steps > 0) {
-#pragma unroll
-    for (int s = 0; s < AHEAD; ++s) issue(s);
-    const unsigned lane_off = (unsigned)((8 * (lane >> 5) + ((lane & 15) >> 2)) * 64 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8);
-    // lo tile: row (8 kh + (i >> 1)) * 32 + slot parity a * 16 + (i & 1) * 8, i = lane & 15
-    const unsigned lane_off8 = (unsigned)((8 * (lane >> 5) + ((lane & 15) >> 1)) * 32 + ((lane >> 4) & 1) * 16 + (lane & 1) * 8);
-    const int kh = lane >> 5;
-    for (int s = 0; s < n_steps; ++s) {
-      if (wave == 0) wait_vmcnt<(AHEAD - 1) * (NDMA + 1)>(); else
-      wait_vmcnt<(AHEAD - 1) * NDMA>();
-      __syncthreads();
-      issue(s + AHEAD);      // see wgrad_body_tr
-      if (active) {
-        const char* ring0 = smem + (s % WGTR_NBUF) * STEP_BYTES;
-        const char* ring = ring0 + lane_off;
-        const char* ring8 = ring0 + lane_off8;
-        const float4 s0 = *(const float4*)(ring0 + L8::SCALES + kh * 32), s1 = *(const float4*)(ring0 + L8::SCALES + kh * 32 + 16);
-        const half8 sc8 = {(_Float16)(s0.x * inv_mref), (_Float16)(s0.y * inv_mref), (_Float16)(s0.z * inv_mref), (_Float16)(s0.w * inv_mref),
-                           (_Float16)(s1.x * inv_mref), (_Float16)(s1.y * inv_mref), (_Float16)(s1.z * inv_mref), (_Float16)(s1.w * inv_mref)};
-        half8 beh, bel;
-        if constexpr (SH::EXTRA) {
-          beh = tr_read8(ring + (KT + NT - 1) * 1024);
-          bel = lo8_decode(tr_read8b(ring8 + L8::LOD + (NT - 1) * 512), LO8_SCALE_D);
-        }
-        static_assert(SH::WK >= TN, "bias owners");
-        auto read_a = [&](int i, half8& h, half8& l) {
-          const int t = wk * TK + i;
-          h = tr_read8(ring + t * 1024) * sc8;
-          l = lo8_decode(tr_read8b(ring8 + L8::LOX + t * 512), LO8_SCALE_X) * sc8;
-        };
-        auto read_b = [&](int j, half8& h, half8& l) {
-          const int nt = wn * TN + j;
-          h = tr_read8(ring + (KT + nt) * 1024);
-          l = lo8_decode(tr_read8b(ring8 + L8::LOD + nt * 512), LO8_SCALE_D);
-        };
-        auto dot8 = [&](const half8& x, float c) -> float {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) c = __builtin_amdgcn_fdot2(half2v{sc8[2 * k], sc8[2 * k + 1]}, half2v{x[2 * k], x[2 * k + 1]}, c, false);
-          return c;
-        };
-        auto bias_row = [&](int j, const half8& h, const half8& l) {
-          if (wk == j) { accb = dot8(h, accb); accb = dot8(l, accb); }
-        };
-        half8 ae_h, ae_l;
-        if constexpr (TK > TN) {            // B resident, A streams
-          half8 bh[TN], bl[TN];
-#pragma unroll
-          for (int j = 0; j < TN; ++j) read_b(j, bh[j], bl[j]);
-          half8 an_h, an_l;
-          read_a(0, an_h, an_l);
-#pragma unroll
-          for (int i = 0; i < TK; ++i) {
-            const half8 ah = an_h, al = an_l;
-            if (i + 1 < TK) read_a(i + 1, an_h, an_l);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = mfma_h8(ah, bh[j], acc[i][j]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = mfma_h8(ah, bl[j], acc[i][j]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = mfma_h8(al, bh[j], acc[i][j]);
-          }
-#pragma unroll
-          for (int j = 0; j < TN; ++j) bias_row(j, bh[j], bl[j]);
-        } else {                            // A resident, B streams in chunks of NCH n-tiles
-          constexpr int NCH = WGTR_NCH < TN ? WGTR_NCH : TN;
-          static_assert(TN % NCH == 0, "n-tile chunks");
-          half8 ah[TK], al[TK];
-#pragma unroll
-          for (int i = 0; i < TK; ++i) read_a(i, ah[i], al[i]);
-#pragma unroll
-          for (int c = 0; c < TN / NCH; ++c) {
-            half8 bh[NCH], bl[NCH];
-#pragma unroll
-            for (int jj = 0; jj < NCH; ++jj) read_b(c * NCH + jj, bh[jj], bl[jj]);
-#pragma unroll
-            for (int i = 0; i < TK; ++i)
-#pragma unroll
-              for (int jj = 0; jj < NCH; ++jj) acc[i][c * NCH + jj] = mfma_h8(ah[i], bh[jj], acc[i][c * NCH + jj]);
-#pragma unroll
-            for (int i = 0; i < TK; ++i)
-#pragma unroll
-              for (int jj = 0; jj < NCH; ++jj) acc[i][c * NCH + jj] = mfma_h8(ah[i], bl[jj], acc[i][c * NCH + jj]);
-#pragma unroll
-            for (int i = 0; i < TK; ++i)
-#pragma unroll
-              for (int jj = 0; jj < NCH; ++jj) acc[i][c * NCH + jj] = mfma_h8(al[i], bh[jj], acc[i][c * NCH + jj]);
-#pragma unroll
-            for (int jj = 0; jj < NCH; ++jj) bias_row(c * NCH + jj, bh[jj], bl[jj]);
-          }
-          if constexpr (SH::EXTRA) { ae_h = wn ? ah[1] : ah[0]; ae_l = wn ? al[1] : al[0]; }
-        }
-        if constexpr (SH::EXTRA) {
-          static_assert(!SH::EXTRA || TK <= TN, "the extra tile reads the resident A fragments");
-          acce = mfma_h8(ae_h, beh, acce);
-          acce = mfma_h8(ae_h, bel, acce);
-          acce = mfma_h8(ae_l, beh, acce);
-        }
-      }
-    }
-    wait_vmcnt<0>();
-  }
-  constexpr size_t ldn = (size_t)NT * 32;
-  const int m = lane & 31, h = lane >> 5;
-  if (active) {
-#pragma unroll
-    for (int i = 0; i < TK; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-          pg[(size_t)((wk * TK + i) * 32 + row) * ldn + (wn * TN + j) * 32 + m] = acc[i][j][r];
-        }
-    if constexpr (SH::EXTRA) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-        pg[(size_t)((wk * TK + wn) * 32 + row) * ldn + (NT - 1) * 32 + m] = acce[r];
-      }
-    }
-    const float bsum = accb + __shfl_xor(accb, 32);
-    if (wk < TN && h == 0) pbias[(wn * TN + wk) * 32 + m] = bsum;
-  }
-}
-
 // At most 224 VGPRs per wave: two of these waves per SIMD then leave 64 registers — one wave of the march kernel — on every SIMD, so
 // the next batch's march (a latency-bound chain that needs a wave slot on every CU, no LDS) can be co-resident with this HBM-paced kernel
 // instead of waiting for whole CUs to drain.
 constexpr int WGRAD_VGPRS = 112;      // the attribute counts half of the unified VGPR + AGPR file on gfx90a+: 112 -> 224 registers
-template <int NP>
+template <class Planes>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(WGRAD_VGPRS)))
 nerfmlp_wgrad_tr_kernel(const uint4* __restrict__ saved, const uint4* __restrict__ dy, long long R, float* __restrict__ workspace, const WgradTable tab,
                         long long* __restrict__ trace) {
@@ -2118,31 +2000,7 @@ nerfmlp_wgrad_tr_kernel(const uint4* __restrict__ saved, const uint4* __restrict
   const WgTrSegs sg = {tab.qx[j], job.KTa, tab.qx2[j], tab.qd[j], job.NTa, tab.KSd[j], tab.qd2[j], tab.KSd2[j]};
 #define RNERF_WGRAD_CASE(KT_, NT_)                                                                                                  \
   if (KT == (KT_) && NT == (NT_)) {                                                                                                 \
-    wgrad_body_tr<NP, KT_, NT_>(saved, dy, R, pg, pb, sg, g, G, smem);                                                              \
-    if (trace && threadIdx.x == 0) trace[2 * blockIdx.x + 1] = (long long)__builtin_amdgcn_s_memrealtime();                         \
-    return;                                                                                                                         \
-  }
-  RNERF_WGRAD_CASE(8, 8) RNERF_WGRAD_CASE(2, 8) RNERF_WGRAD_CASE(10, 8) RNERF_WGRAD_CASE(8, 9) RNERF_WGRAD_CASE(9, 4) RNERF_WGRAD_CASE(4, 1)
-#undef RNERF_WGRAD_CASE
-  __builtin_trap();
-}
-
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(WGRAD_VGPRS)))
-nerfmlp_wgrad_tr8_kernel(const uint4* __restrict__ saved, const uint4* __restrict__ dy, long long R, float* __restrict__ workspace, const WgradTable tab,
-                         long long* __restrict__ trace) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  if (trace && threadIdx.x == 0) trace[2 * blockIdx.x] = (long long)__builtin_amdgcn_s_memrealtime();
-  int j = 0;
-  while ((int)blockIdx.x >= tab.wg0[j + 1]) ++j;
-  const WgradJob job = tab.job[j];
-  const int g = blockIdx.x - tab.wg0[j], G = tab.wg0[j + 1] - tab.wg0[j];
-  const int KT = job.KT, NT = job.NT;
-  float* pg = workspace + tab.poff[j] + (size_t)g * (size_t)KT * 32 * NT * 32;
-  float* pb = workspace + tab.pboff[j] + (size_t)g * NT * 32;
-  const WgTrSegs sg = {tab.qx[j], job.KTa, tab.qx2[j], tab.qd[j], job.NTa, tab.KSd[j], tab.qd2[j], tab.KSd2[j]};
-#define RNERF_WGRAD_CASE(KT_, NT_)                                                                                                  \
-  if (KT == (KT_) && NT == (NT_)) {                                                                                                 \
-    wgrad_body_tr8<KT_, NT_>(saved, dy, R, pg, pb, sg, g, G, smem);                                                                 \
+    wgrad_body_tr<Planes, KT_, NT_>(saved, dy, R, pg, pb, sg, g, G, smem);                                                          \
     if (trace && threadIdx.x == 0) trace[2 * blockIdx.x + 1] = (long long)__builtin_amdgcn_s_memrealtime();                         \
     return;                                                                                                                         \
   }
@@ -3435,6 +3293,18 @@ extern "C" size_t rnerf_nerfmlp_wgrad_workspace_bytes(void) {
   return w.partial_floats * sizeof(float) + (size_t)w.max_wgs * 2 * sizeof(long long);       // + the RNERF_WGRAD_TRACE slots
 }
 
+// host side of the transposing wgrad for one operand format; launch returns where the dgrad left m_ref (behind the row scales)
+template <class Planes> struct WgradTrHost {
+  static hipError_t allow_lds() {
+    return hipFuncSetAttribute((const void*)nerfmlp_wgrad_tr_kernel<Planes>, hipFuncAttributeMaxDynamicSharedMemorySize, Planes::lds_bytes());
+  }
+  static const float* launch(const WgradTable& tab, hipStream_t st, const void* save, const void* dy, long long R, void* workspace, long long* trace) {
+    hipLaunchKernelGGL(nerfmlp_wgrad_tr_kernel<Planes>, dim3(tab.wg0[tab.n]), dim3(512), Planes::lds_bytes(), st, (const uint4*)save, (const uint4*)dy, R,
+                       (float*)workspace, tab, trace);
+    return (const float*)((const uint4*)dy + dy_plane_uint4(R, Planes::NPLANES)) + R;
+  }
+};
+
 extern "C" int rnerf_nerfmlp_wgrad(int fwd_precision, int backward, const void* save, const void* dy, int64_t rows, float* grads, void* workspace,
                                    void* stream) {
   RNERF_CHECK_ARG(save && dy && grads && workspace, "rnerf_nerfmlp_wgrad: null pointer");
@@ -3446,9 +3316,9 @@ extern "C" int rnerf_nerfmlp_wgrad(int fwd_precision, int backward, const void* 
   if (ready.need()) {
     RNERF_CHECK_HIP(hipFuncSetAttribute((const void*)nerfmlp_wgrad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
     RNERF_CHECK_HIP(hipFuncSetAttribute((const void*)nerfmlp_wgrad_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
-    RNERF_CHECK_HIP(hipFuncSetAttribute((const void*)nerfmlp_wgrad_tr_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, wgtr_lds_bytes<1>()));
-    RNERF_CHECK_HIP(hipFuncSetAttribute((const void*)nerfmlp_wgrad_tr_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, wgtr_lds_bytes<2>()));
-    RNERF_CHECK_HIP(hipFuncSetAttribute((const void*)nerfmlp_wgrad_tr8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wgtr8_lds_bytes()));
+    RNERF_CHECK_HIP(WgradTrHost<F16Planes<1>>::allow_lds());
+    RNERF_CHECK_HIP(WgradTrHost<F16Planes<2>>::allow_lds());
+    RNERF_CHECK_HIP(WgradTrHost<Lo8Planes>::allow_lds());
     ready.set();
   }
   const long long R = (rows + 255) / 256 * 256;
@@ -3467,17 +3337,11 @@ extern "C" int rnerf_nerfmlp_wgrad(int fwd_precision, int backward, const void* 
       hipLaunchKernelGGL(nerfmlp_wgrad_kernel<true>, dim3(tab.wg0[tab.n]), dim3(512), 131072, st, (const uint4*)save, (const uint4*)dy, R,
                          (long long)rows, n_chunks, (float*)workspace, tab);
   } else if (backward == RNERF_BWD_F16) {
-    hipLaunchKernelGGL(nerfmlp_wgrad_tr_kernel<1>, dim3(tab.wg0[tab.n]), dim3(512), wgtr_lds_bytes<1>(), st, (const uint4*)save, (const uint4*)dy, R,
-                       (float*)workspace, tab, trace);
-    out_scale = (const float*)((const uint4*)dy + dy_plane_uint4(R, 1)) + R;
+    out_scale = WgradTrHost<F16Planes<1>>::launch(tab, st, save, dy, R, workspace, trace);
   } else if (backward == RNERF_BWD_F16X3_LO8) {
-    hipLaunchKernelGGL(nerfmlp_wgrad_tr8_kernel, dim3(tab.wg0[tab.n]), dim3(512), wgtr8_lds_bytes(), st, (const uint4*)save, (const uint4*)dy, R,
-                       (float*)workspace, tab, trace);
-    out_scale = (const float*)((const uint4*)dy + dy_plane_uint4(R, 2)) + R;
+    out_scale = WgradTrHost<Lo8Planes>::launch(tab, st, save, dy, R, workspace, trace);
   } else {
-    hipLaunchKernelGGL(nerfmlp_wgrad_tr_kernel<2>, dim3(tab.wg0[tab.n]), dim3(512), wgtr_lds_bytes<2>(), st, (const uint4*)save, (const uint4*)dy, R,
-                       (float*)workspace, tab, trace);
-    out_scale = (const float*)((const uint4*)dy + dy_plane_uint4(R, 2)) + R;
+    out_scale = WgradTrHost<F16Planes<2>>::launch(tab, st, save, dy, R, workspace, trace);
   }
   int max_elems = 0;
   for (int j = 0; j < tab.n; ++j) max_elems = tab.job[j].KT * tab.job[j].NT * 1024 > max_elems ? tab.job[j].KT * tab.job[j].NT * 1024 : max_elems;
