@@ -599,6 +599,38 @@ int rnerf_visual_hull_count(const uint8_t* masks, int64_t num_views, int32_t hei
 int rnerf_visual_hull_finalize(const int32_t* count, const rnerf_grid* g, int64_t total_views, double threshold, double ior_inside,
                                double ior_outside, float* out, void* stream);
 
+/* ---- Preview meshes: marching cubes.  Replaces mcubes.marching_cubes at voxelize_mesh.py:122-135 (the voxelised grid's preview OBJ),
+ * calib/make_visual_hull.py:148-157 (the carved hull's) and extract_mesh.py:232-268 (a trained field's density), on a grid that is already
+ * on the device.  Appended; RNERF_VERSION stays 4.  PyMCubes' tie rule, vertex order and per-case triangulation are not reproduced; the
+ * mesh is specified here instead, and is the same bytes on every run (no atomics).
+ * field: float[dims[0]][dims[1]][dims[2]], axis 0 slowest.  A node is solid iff (double)f > iso, so NaN is empty and a plateau equal to iso
+ * has no surface inside it.  Vertices: one per grid edge whose endpoints classify differently, owned by the edge's lower node, in node
+ * order (axis 0 slowest) and within a node x-, y-, z-edge; double[V][3] in index units (sample i sits at coordinate i): the node's index
+ * plus t = (iso - f1) / (f2 - f1) on the edge's axis, in float64 with every operation rounded, f1 the owning node's value; t = 0.5
+ * where that is not within [0, 1] (non-finite endpoints), so every vertex is finite and on its edge.  Triangles: int32[F][3] vertex
+ * indices, in cell order (a cell is named by its lowest node) and within a cell in the order of the case table; counter-clockwise seen
+ * from the empty side, so a closed surface around higher values has a positive signed volume.  The table (tools/make_mc_tables.py)
+ * cuts off each solid corner of an ambiguous face on its own; two cells that share a face agree there, so the surface of any field is
+ * closed and consistently oriented except where it leaves the grid.
+ * Limits (RNERF_ERR_ARG otherwise; checked before any device work): every dim >= 2 and 3 * dims[0] * dims[1] * dims[2] <= 2^31 - 1
+ * (894^3 passes), iso finite, capacities >= 0.
+ *   rnerf_marching_cubes_workspace_bytes: 8 ceil(N / 1024) + 4 N for N nodes (0 with a message for bad dims).
+ *   rnerf_marching_cubes_count: two launches; fills `workspace` (8-byte aligned) and writes totals[0] = V, totals[1] = F (device, int64[2]).
+ *   rnerf_marching_cubes_emit: with the same field, dims, iso and the workspace of _count; two launches.  Rows at or beyond a capacity
+ *     are dropped and *overflow (device, zeroed by this call) is set to 1.  A capacity of 0 (its pointer may then be null) launches
+ *     nothing of that kind and reports no overflow for it.  The vertex launch also writes every node's first vertex index into the
+ *     workspace's per-node part, which the triangle launch reads: a call with verts_capacity 0 and faces_capacity > 0 is valid only
+ *     after a call with verts_capacity > 0 on the same workspace.  What _count left in the workspace is only read, so _emit may be
+ *     repeated.
+ *   rnerf_marching_cubes_table: copies the case table the kernels use to tri_out, host int8[256][16]: up to five triangles of three edge
+ *     ids per case, -1 padded.  Case bit x + 2y + 4z is set where corner (x, y, z) is solid; edge id = 4 axis + a + 2 b, (a, b) the base
+ *     corner's coordinates on the two other axes, the lower axis first.  Needs no device. */
+size_t rnerf_marching_cubes_workspace_bytes(const int32_t dims[3]);
+int rnerf_marching_cubes_count(const float* field, const int32_t dims[3], double iso, void* workspace, int64_t* totals, void* stream);
+int rnerf_marching_cubes_emit(const float* field, const int32_t dims[3], double iso, const void* workspace, double* verts,
+                              int64_t verts_capacity, int32_t* faces, int64_t faces_capacity, int32_t* overflow, void* stream);
+int rnerf_marching_cubes_table(int8_t* tri_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,11 @@ SIGNATURES = {
     "rnerf_visual_hull_pack": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp]),
     "rnerf_visual_hull_count": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _GP, _i32, _vp, _vp, _vp]),
     "rnerf_visual_hull_finalize": (C.c_int, [_vp, _GP, _i64, _dbl, _dbl, _dbl, _vp, _vp]),
+    # preview meshes (csrc/mcubes.hip)
+    "rnerf_marching_cubes_workspace_bytes": (C.c_size_t, [C.POINTER(_i32 * 3)]),
+    "rnerf_marching_cubes_count": (C.c_int, [_vp, C.POINTER(_i32 * 3), _dbl, _vp, _vp, _vp]),
+    "rnerf_marching_cubes_emit": (C.c_int, [_vp, C.POINTER(_i32 * 3), _dbl, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "rnerf_marching_cubes_table": (C.c_int, [_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -3,15 +3,17 @@
     data, ndim, nmin, nmax = from_calib(calib, masks, num_voxels=512, device="cuda:0")     # calib = json.load(open("calib.json"))
     data, ndim, nmin, nmax, count = carve(masks, cam_mat, transforms, 512, return_count=True)
     save_mesh_pkl(path, count, len(transforms), 0.9, nmin, nmax)      # the dict train.py:209-217 / grid.load_mesh_pkl read
+    verts, faces = preview_mesh(count, len(transforms), 0.9, nmin, nmax, out_dir=".")     # mesh_{G}_0_{threshold}.obj
 
 `data` is float32 [G,G,G], x slowest, 1.33 inside the hull and 1.0 outside — the tuple voxelize.voxelize returns, so grid.prepare_grid /
 ops.grid_prefilter take it.  The view and projection matrices are formed on the host in numpy float64 as the reference writes them; the
-G^3 x V projections, the mask lookups and the counts run on the device (rnerf_visual_hull_count, csrc/hull.hip).  Reading image files,
-calibration and the marching-cubes preview mesh the script also exports are not here.
+G^3 x V projections, the mask lookups and the counts run on the device (rnerf_visual_hull_count, csrc/hull.hip); preview_mesh is the
+hull's marching-cubes mesh the script also exports (:148-157).  Reading image files and calibration are not here.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 import pickle
 from typing import Optional
 
@@ -138,3 +140,34 @@ def save_mesh_pkl(path: str, count, num_views: int, threshold: float, min_point,
     with open(path, "wb") as f:
         pickle.dump({"data": (frac > threshold).reshape(-1, 1) * 0.33 + 1.0, "extent": 0, "min_point": np.asarray(min_point, np.float64),
                      "max_point": np.asarray(max_point, np.float64), "num_voxels": int(c.shape[0])}, f)
+
+
+def preview_coords(verts, num_voxels: int, min_point, max_point):
+    """:151-154: marching-cubes vertices (index units) / num_voxels, scaled into the box.  (The voxel centres divide by num_voxels - 1,
+    :112-120; the script's mesh is smaller than the grid by that factor, and so is this one.)"""
+    lo = np.asarray(min_point, np.float64); span = np.asarray(max_point, np.float64) - lo
+    den = np.full(3, float(num_voxels))
+    if isinstance(verts, torch.Tensor):            # the divisor as a tensor: torch multiplies by the reciprocal of a Python scalar
+        lo, span, den = (torch.from_numpy(a).to(verts.device) for a in (lo, span, den))
+    return verts / den * span + lo
+
+
+def preview_mesh(count, num_views: int, threshold: float, min_point, max_point, out_dir: Optional[str] = None, device=None):
+    """calib/make_visual_hull.py:148-157: marching cubes of the boolean grid count / num_views > threshold (float64, as :136) at iso 0.5,
+    vertices in the script's own transform (preview_coords). -> (verts float64 [V,3], faces int32 [F,3]) on the device; with out_dir the
+    OBJ is written there as mesh_{G}_0_{threshold}.obj.  Every vertex sits half way along a grid edge.  The mesh is marching_cubes.py's,
+    not PyMCubes' vertex for vertex."""
+    from . import marching_cubes as mc
+    c = count if isinstance(count, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(count))
+    if c.ndim != 3 or not (c.shape[0] == c.shape[1] == c.shape[2]):
+        raise ValueError(f"count must be [G, G, G], got {tuple(c.shape)}")
+    G = int(c.shape[0])
+    if device is not None:
+        c = c.to(device)
+    elif not c.is_cuda:
+        c = c.to(torch.device("cuda", torch.cuda.current_device()))
+    verts, faces = mc.marching_cubes(c.to(torch.float64) / num_views > threshold, 0.5)
+    verts = preview_coords(verts, G, min_point, max_point)
+    if out_dir is not None:
+        mc.save_obj(os.path.join(out_dir, f"mesh_{G}_0_{threshold}.obj"), verts, faces)
+    return verts, faces

@@ -2,6 +2,7 @@
 
     data, ndim, nmin, nmax = voxelize(verts, faces, num_voxels=128, extent=1.5, num_samples=4, device="cuda:0")
     save_mesh_pkl(path, data, extent=1.5, num_voxels=128)        # the dict train.py:209-217 / grid.load_mesh_pkl read
+    verts, faces = preview_mesh(data, threshold=1.165, num_samples=4, extent=1.5, out_dir=".")     # the script's preview OBJ (:122-135)
 
 `data` is the raw voxel value (mean IoR in [1, 1.33]) as float32 [G,G,G], x slowest — feed it to grid.prepare / ops.grid_prefilter.
 Point-in-mesh = parity of surface crossings along +z (watertight meshes), evaluated in fp64 with the top-left rule on shared
@@ -10,6 +11,7 @@ edges; pysdf's robust mode may differ on points that lie exactly on the surface 
 from __future__ import annotations
 
 import ctypes as C
+import os
 import pickle
 from typing import Optional, Sequence, Tuple
 
@@ -148,3 +150,56 @@ def save_mesh_pkl(path: str, data, extent: float = 0.0, min_point=(-1, -1, -1), 
     with open(path, "wb") as f:
         pickle.dump({"data": a.astype(np.float64).reshape(-1, 1), "extent": extent, "min_point": list(min_point), "max_point": list(max_point),
                      "num_voxels": G}, f)
+
+
+def preview_coords(verts, num_voxels: int):
+    """voxelize_mesh.py:133: marching-cubes vertices (index units) / N - 0.5, the coordinates of the script's OBJ."""
+    den = np.full(3, float(num_voxels))
+    if isinstance(verts, torch.Tensor):            # the divisor as a tensor: torch multiplies by the reciprocal of a Python scalar
+        den = torch.from_numpy(den).to(verts.device)
+    return verts / den - 0.5
+
+
+def world_coords(verts, ndim, nmin, nmax):
+    """Marching-cubes vertices (index units) in the grid's own world coordinates: sample i of an axis sits at nmin + i / (N - 1) * (nmax - nmin)
+    (voxelize_mesh.py:84-96).  The script's OBJ is not in these: it divides by N and ignores the extent."""
+    lo = np.asarray(nmin, np.float64); span = np.asarray(nmax, np.float64) - lo
+    den = np.asarray(ndim, np.float64) - 1.0
+    if isinstance(verts, torch.Tensor):
+        lo, span, den = (torch.from_numpy(a).to(verts.device) for a in (lo, span, den))
+    return verts / den * span + lo
+
+
+def preview_name(num_samples: int, num_voxels: int, extent: float, threshold: float) -> str:
+    """The file name of voxelize_mesh.py:135."""
+    return f"mesh_{num_samples}_{num_voxels}_{extent}_{threshold}.obj"
+
+
+def preview_mesh(data, threshold: float = 1.0, num_samples: int = 4, extent: float = 3.0, out_dir: Optional[str] = None, device=None):
+    """voxelize_mesh.py:122-135: the iso-surface of the voxelised grid at `threshold`, vertices / N - 0.5 as the script exports them.
+    -> (verts float64 [V,3], faces int32 [F,3]) on the device; with out_dir the OBJ is written there under the script's file name, for which
+    alone num_samples and extent are used.  data: [G,G,G] (or the [G^3, 1] of mesh.pkl), x slowest.  The mesh is marching_cubes.py's, not
+    PyMCubes' vertex for vertex."""
+    from . import marching_cubes as mc
+    f = data if isinstance(data, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(data))
+    if f.ndim != 3:
+        G = round(f.numel() ** (1.0 / 3.0))
+        f = f.reshape(G, G, G)
+    N = int(f.shape[0])
+    verts, faces = mc.marching_cubes(f, threshold, device=device)
+    verts = preview_coords(verts, N)
+    if out_dir is not None:
+        mc.save_obj(os.path.join(out_dir, preview_name(num_samples, N, extent, threshold)), verts, faces)
+    return verts, faces
+
+
+def preview_mesh_world(data, threshold: float = 1.0, extent: float = 0.0, min_point=(-1, -1, -1), max_point=(1, 1, 1), device=None):
+    """preview_mesh's surface in the grid's world coordinates (world_coords), the frame voxelize() took its mesh in."""
+    from . import marching_cubes as mc
+    f = data if isinstance(data, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(data))
+    if f.ndim != 3:
+        G = round(f.numel() ** (1.0 / 3.0))
+        f = f.reshape(G, G, G)
+    nmin, nmax = ([-float(extent)] * 3, [float(extent)] * 3) if extent > 0 else (list(min_point), list(max_point))
+    verts, faces = mc.marching_cubes(f, threshold, device=device)
+    return world_coords(verts, list(f.shape), nmin, nmax), faces
