@@ -37,8 +37,8 @@ extern "C" {
  * stream (rnerf_nerfmlp_packed_bytes grew) — and this round's additions: enum rnerf_backward gains F16X3_LO8, rnerf_sample_batch.
  * 4: the opt-in schedule fields no caller set are gone.  rnerf_train_cfg ends with aux_stream, grads_stream (nothing in between);
  * rnerf_prefetch ends with side_stream (the march always forks right before the last NerfMLP wgrad); rnerf_bkgd_backward is the only
- * background-MLP backward entry point.  Still 4 with rnerf_flip / rnerf_flip_workspace_bytes and with rnerf_visual_hull_*: they are appended, no
- * existing entry point or struct moved. */
+ * background-MLP backward entry point.  Still 4 with rnerf_flip / rnerf_flip_workspace_bytes, rnerf_visual_hull_*, rnerf_marching_cubes_*,
+ * rnerf_mesh_depth and rnerf_mask_dilate: they are appended, no existing entry point or struct moved. */
 #define RNERF_VERSION 4
 
 enum rnerf_status {
@@ -630,6 +630,62 @@ int rnerf_marching_cubes_count(const float* field, const int32_t dims[3], double
 int rnerf_marching_cubes_emit(const float* field, const int32_t dims[3], double iso, const void* workspace, double* verts,
                               int64_t verts_capacity, int32_t* faces, int64_t faces_capacity, int32_t* overflow, void* stream);
 int rnerf_marching_cubes_table(int8_t* tri_out);
+
+/* ---- Evaluation masks: the silhouette of a mesh.  Replaces the pyrender depth render of metric/render_mask.py:84-91 (an OpenGL context)
+ * by a rasteriser over the camera model of rnerf_generate_rays.  Appended; RNERF_VERSION stays 4.
+ * verts: double[V][3] world coordinates; faces: int32[F][3], every index in [0, V) — the caller's responsibility, they are not checked on
+ * the device; camtoworld .. pixel_center: exactly the arguments of rnerf_generate_rays (opencv = 0: Blender model, cx = W/2, cy = H/2).
+ * Pixel (row, col) is covered by a face iff the ray rnerf_generate_rays makes for it passes through the face, decided in float64 with every
+ * operation rounded, as a 2-D test on the image plane:
+ *   camera space   (xc, yc, zc) = Ri (p - t), each component ((Ri_j0 d0 + Ri_j1 d1) + Ri_j2 d2); t = camtoworld's translation widened from
+ *                    float32, Ri = the inverse of its rotation widened from float32 (adjugate / determinant, formed on the host) — not
+ *                    the transpose: a float32 rotation is orthogonal to about 1e-8 only, and the pixel's ray is t + lambda R cam;
+ *   depth          = zc (OpenCV) or -zc (Blender): the distance along the view axis, what pyrender's depth buffer and Blender's Z pass
+ *                    hold, not the ray parameter of the normalised viewdir;
+ *   projection     X = (xc fx) / depth + cx,  Y = ((sy yc) fy) / depth + cy,  sy = -1 (Blender) or +1 (OpenCV),  w = 1 / depth,
+ *                    fx, fy, cx, cy, pixel_center rounded to float32 first (as rnerf_generate_rays holds them);
+ *   sample point   (x, y) = (col + pixel_center, row + pixel_center);
+ *   orientation    area = (Bx - Ax)(Cy - Ay) - (By - Ay)(Cx - Ax); zero area covers nothing; sgn = +-1 its sign: either winding is
+ *                    drawn (the Blender model mirrors the image plane), there is no back-face culling;
+ *   edge function  of the edge P -> Q (AB, BC, CA): with (p, q) = (P, Q) if P <= Q lexicographically by (X, then Y), else (Q, P) and
+ *                    s = sgn or -sgn accordingly, e = ((qx - px)(y - py) - (qy - py)(x - px)) s.  The two faces of a shared edge of a
+ *                    consistently oriented mesh evaluate the same rounded expression with opposite signs;
+ *   fill rule      inside the edge iff e > 0, or e == 0 and (dy > 0 or (dy == 0 and dx < 0)) with (dx, dy) = ((Qx - Px) sgn,
+ *                    (Qy - Py) sgn): the top-left rule of rnerf_voxelize.  A sample on a shared edge belongs to exactly one of its two
+ *                    faces, one on a vertex to exactly one face of the fan;
+ *   depth          = (eab + ebc + eca) / ((ebc wA + eca wB) + eab wC) (perspective-correct: 1 / depth is linear in the weights), a hit
+ *                    only where the first sum is > 0; kept iff znear < depth < zfar.
+ * A face is tested at the pixels of the 16 x 16 pixel tiles (tile (i, j) = rows 16 i .., columns 16 j ..) that its pixel bounding box,
+ * widened by one pixel on every side, meets — which matters only for what rounding could do far outside a degenerate face.
+ * Outputs, none of which depends on the order of the face list or of any atomic: depth float[H][W] = float32 of the smallest kept depth,
+ * 0 = nothing (render_mask.py:91 tests `depth != 0`); tri (nullable) int32[H][W] = the lowest face index among the hits that attain that
+ * smallest float64 depth, -1 = nothing; hits (nullable) int32[H][W] = the number of kept hits (even everywhere for a closed mesh seen from
+ * outside and inside [znear, zfar]).  The same inputs give the same bytes on every run, and a permuted face list the same depth and hits.
+ * A face with a vertex at or behind the camera plane (depth <= 0, or a projection that is not finite) is not drawn and is counted in
+ * *skipped (device int64[1], written by every call): there is no clipping, a camera inside the object is not a use of this.
+ * Everything after the caller's upload runs on the device: projection, per-face tile range, per-tile lists (count, fixed-order scan, fill
+ * through a cursor; a face that meets more than 4 tiles goes to one list that every tile walks, so the workspace depends on the sizes only).
+ * num_faces == 0 is valid: the empty image, nothing that indexes the mesh is launched (verts, faces, workspace may be null).
+ * RNERF_ERR_ARG before any device work: null camtoworld / depth / skipped, null verts / faces / workspace or num_verts == 0 with
+ * num_faces > 0, num_verts outside [0, 2^31), num_faces outside [0, 2^29), H or W < 1, H * W >= 2^31, opencv not 0 / 1, fx or fy zero or
+ * not finite, cx / cy / pixel_center not finite, a rotation without a finite inverse, not znear < zfar, verts / skipped not 8-byte or workspace not 16-byte aligned.
+ *   rnerf_mesh_depth_workspace_bytes: 24 V + 36 F + 8 tiles + O(1), each part rounded up to 16 bytes (0 with a message for a bad size). */
+size_t rnerf_mesh_depth_workspace_bytes(int64_t num_verts, int64_t num_faces, int32_t height, int32_t width);
+int rnerf_mesh_depth(const double* verts, int64_t num_verts, const int32_t* faces, int64_t num_faces, const float* camtoworld /* HOST [3][4] */,
+                     int32_t opencv, double fx, double fy, double cx, double cy, double pixel_center, int32_t height, int32_t width,
+                     double znear, double zfar, float* depth, int32_t* tri, int32_t* hits, int64_t* skipped, void* workspace, void* stream);
+
+/* ---- Evaluation masks: cv2.dilate(mask, np.ones((ky, kx)), iterations=1) with cv2's defaults (render_mask.py:92-93: 35 x 35) and
+ * cv2.boundingRect of the result (metric/summary.py:202).  mask: uint8[H][W], > 0 = set; out: uint8[H][W], 255 where any pixel of the
+ * ky x kx box centred on the pixel is set, else 0; pixels outside the image do not contribute.  A row pass into the workspace, then a
+ * column pass.  bbox (nullable): device int32[4] = (x, y, w, h): the smallest set column and row of `out` and the extent to the largest,
+ * both inclusive; (0, 0, 0, 0) when nothing is set.  It is reduced from one partial rectangle per 256 pixels in a fixed order (integer
+ * minima and maxima).  RNERF_ERR_ARG before any device work: null mask / out / workspace, H or W < 1, H * W >= 2^31, ky or kx even or
+ * < 1, out overlapping mask, workspace not 16-byte aligned.
+ *   rnerf_mask_dilate_workspace_bytes: H W rounded up to 16, + 16 ceil(H W / 256) (0 with a message for a bad size). */
+size_t rnerf_mask_dilate_workspace_bytes(int32_t height, int32_t width);
+int rnerf_mask_dilate(const uint8_t* mask, int32_t height, int32_t width, int32_t ky, int32_t kx, uint8_t* out, int32_t* bbox,
+                      void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

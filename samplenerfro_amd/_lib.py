@@ -169,6 +169,11 @@ SIGNATURES = {
     "rnerf_marching_cubes_count": (C.c_int, [_vp, C.POINTER(_i32 * 3), _dbl, _vp, _vp, _vp]),
     "rnerf_marching_cubes_emit": (C.c_int, [_vp, C.POINTER(_i32 * 3), _dbl, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "rnerf_marching_cubes_table": (C.c_int, [_vp]),
+    # evaluation masks (csrc/raster.hip)
+    "rnerf_mesh_depth_workspace_bytes": (C.c_size_t, [_i64, _i64, _i32, _i32]),
+    "rnerf_mesh_depth": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _i32, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rnerf_mask_dilate_workspace_bytes": (C.c_size_t, [_i32, _i32]),
+    "rnerf_mask_dilate": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

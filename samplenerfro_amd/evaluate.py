@@ -4,6 +4,8 @@
 with utils.render_image (pipelined form), scores it on the device — PSNR of the device MSE (utils.compute_psnr) and SSIM with max_val 1
 (utils.compute_ssim, rnerf_ssim) — and reads back two floats per view.  With save_output it writes the reference's files.  With flip=True
 each view is also scored with LDR-FLIP (utils.compute_flip, rnerf_flip; metric/summary.py:72-78) and the read-back carries three floats.
+With masks / mask_mode the views are scored on the object's region and / or the crop around it (summary.py:91-92,177-205,
+metric/compare.py:132-133,167-197; the masks come from mesh_mask.render_masks).
 """
 from __future__ import annotations
 
@@ -35,27 +37,61 @@ def device_views(images, camtoworlds, *, focal: Optional[float] = None, cam_mat=
         yield {"rays": Rays(o, None, v, None), "pixels": pix}
 
 
-def write_metric_files(out_dir: str, step, psnr_values, ssim_values, flip_values=None) -> None:
+MASK_MODES = ("mask", "crop", "mask_crop")
+
+
+def mask_suffix(mask_mode: Optional[str]) -> str:
+    """What metric/summary.py:165 evaluates to, `"_mask" if MASK else "" + "_crop" if CROP else ""`.  The conditional expression binds
+    more loosely than `+`, so this is "_mask" whenever MASK is set — for "mask" and also for "mask_crop" — and "_crop" for "crop"."""
+    if mask_mode is None:
+        return ""
+    if mask_mode not in MASK_MODES:
+        raise ValueError(f"mask_mode must be one of {MASK_MODES} or None, got {mask_mode!r}")
+    return "_crop" if mask_mode == "crop" else "_mask"
+
+
+def write_metric_files(out_dir: str, step, psnr_values, ssim_values, flip_values=None, suffix: str = "") -> None:
     """eval.py:207-215: psnrs_{step}.txt / ssims_{step}.txt (the values joined by spaces) and psnr.txt / ssim.txt (their means).  With
-    flip_values also flips_{step}.txt / flip.txt in the same style (not files of the reference)."""
-    with open(os.path.join(out_dir, f"psnrs_{step}.txt"), "w") as f:
+    flip_values also flips_{step}.txt / flip.txt in the same style (not files of the reference).  suffix (mask_suffix) goes before
+    ".txt" in every name."""
+    with open(os.path.join(out_dir, f"psnrs_{step}{suffix}.txt"), "w") as f:
         f.write(" ".join([str(v) for v in psnr_values]))
-    with open(os.path.join(out_dir, f"ssims_{step}.txt"), "w") as f:
+    with open(os.path.join(out_dir, f"ssims_{step}{suffix}.txt"), "w") as f:
         f.write(" ".join([str(v) for v in ssim_values]))
-    with open(os.path.join(out_dir, "psnr.txt"), "w") as f:
+    with open(os.path.join(out_dir, f"psnr{suffix}.txt"), "w") as f:
         f.write("{}".format(np.mean(np.array(psnr_values))))
-    with open(os.path.join(out_dir, "ssim.txt"), "w") as f:
+    with open(os.path.join(out_dir, f"ssim{suffix}.txt"), "w") as f:
         f.write("{}".format(np.mean(np.array(ssim_values))))
     if flip_values is not None:
-        with open(os.path.join(out_dir, f"flips_{step}.txt"), "w") as f:
+        with open(os.path.join(out_dir, f"flips_{step}{suffix}.txt"), "w") as f:
             f.write(" ".join([str(v) for v in flip_values]))
-        with open(os.path.join(out_dir, "flip.txt"), "w") as f:
+        with open(os.path.join(out_dir, f"flip{suffix}.txt"), "w") as f:
             f.write("{}".format(np.mean(np.array(flip_values))))
+
+
+def apply_mask(pred_color: torch.Tensor, pixels: torch.Tensor, mask, mask_mode: str, min_size: int = 11):
+    """summary.py:197-205 for one view: -> (pred_color, pixels) multiplied by the mask ("mask", "mask_crop") and then cut to the mask's
+    bounding rectangle ("crop", "mask_crop").  mask: [H, W] (or [H, W, 1]), > 0 = set.  min_size: the SSIM window."""
+    from . import mesh_mask
+    H, W = int(pred_color.shape[0]), int(pred_color.shape[1])
+    m = mesh_mask._as_mask(mask, pred_color.device)
+    if tuple(m.shape) != (H, W):
+        raise ValueError(f"evaluate: a mask of shape {tuple(m.shape)} for a view of {H} x {W}")
+    if mask_mode in ("mask", "mask_crop"):
+        mf = m.to(torch.float32)[..., None]
+        pred_color, pixels = pred_color * mf, pixels * mf
+    if mask_mode in ("crop", "mask_crop"):
+        x, y, w, h = mesh_mask.bounding_rect(m)
+        if w < min_size or h < min_size:
+            raise ValueError(f"evaluate: the mask's bounding rectangle is {w} x {h} pixels (an empty mask gives 0 x 0), smaller than the "
+                             f"{min_size} x {min_size} SSIM window")
+        pred_color, pixels = pred_color[y:y + h, x:x + w].contiguous(), pixels[y:y + h, x:x + w].contiguous()
+    return pred_color, pixels
 
 
 def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192, normalize_disp: bool = False, out_dir: Optional[str] = None,
              step=None, save_output: bool = False, render_path: bool = False, flip: bool = False,
-             flip_pixels_per_degree: Optional[float] = None) -> dict:
+             flip_pixels_per_degree: Optional[float] = None, masks=None, mask_mode: Optional[str] = None) -> dict:
     """Render and score every view (eval.py:155-215).
 
     model / variables: what models.construct_nerf returns; views: batches as device_views yields them; rng: the render key (eval.py passes
@@ -67,7 +103,20 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
 
     flip=True also scores each view with utils.compute_flip(pred_color, pixels, flip_pixels_per_degree) (None: compute_ldrflip's default;
     utils.FLIP_PPD_SUMMARY is what metric/summary.py uses): the result gains "flips" and "flip", save_output also writes
-    flips_{step}.txt and flip.txt.  With flip=False the keys, the files and the launches are those of the loop without it."""
+    flips_{step}.txt and flip.txt.  With flip=False the keys, the files and the launches are those of the loop without it.
+
+    masks + mask_mode: the reference's masked / cropped scores (metric/summary.py MASK / CROP).  masks: one [H, W] mask per view (a
+    sequence or iterable of tensors or arrays, e.g. mesh_mask.render_masks; > 0 = set, so 0 / 255 and 0 / 1 both do); mask_mode "mask":
+    pred_color and pixels are multiplied by the mask before scoring (summary.py:197-199); "crop": both are cut to the mask's bounding
+    rectangle (:201-205); "mask_crop": both, in that order.  The metrics are the same device kernels on those images; PSNR is the mean
+    over every pixel of the (cropped) image as there, not normalised by the mask's area.  The metric files carry mask_suffix(mask_mode)
+    before ".txt" — "_mask" for "mask" AND for "mask_crop", "_crop" for "crop": summary.py:165's `"_mask" if MASK else "" + "_crop" if
+    CROP else ""` parses that way.  The PNGs are written unmasked.  The result gains "mask_mode".  A crop smaller than the SSIM window
+    is a ValueError, and so is masks without mask_mode or the reverse; with neither, nothing changes."""
+    if (masks is None) != (mask_mode is None):
+        raise ValueError("evaluate: masks and mask_mode go together (got only one of them)")
+    suffix = mask_suffix(mask_mode)
+    mask_iter = iter(masks) if masks is not None else None
     if save_output:
         if out_dir is None:
             raise ValueError("evaluate: save_output needs out_dir")
@@ -83,11 +132,18 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
         pred_color, pred_disp, _pred_acc = utils.render_image(render_fn, batch["rays"], rng, normalize_disp, chunk=chunk, model=model)
         num_rays += int(pred_color.shape[0]) * int(pred_color.shape[1])
         if not render_path:
-            psnr = utils.compute_psnr(((pred_color - batch["pixels"]) ** 2).mean())
-            ssim = utils.compute_ssim(pred_color, batch["pixels"], max_val=1.0)
+            scored, pixels = pred_color, batch["pixels"]
+            if mask_iter is not None:
+                try:
+                    mask = next(mask_iter)
+                except StopIteration:
+                    raise ValueError(f"evaluate: masks ran out at view {idx}") from None
+                scored, pixels = apply_mask(scored, pixels, mask, mask_mode)
+            psnr = utils.compute_psnr(((scored - pixels) ** 2).mean())
+            ssim = utils.compute_ssim(scored, pixels, max_val=1.0)
             scores = [psnr.to(torch.float32), ssim]
             if flip:
-                scores.append(utils.compute_flip(pred_color, batch["pixels"], flip_pixels_per_degree))
+                scores.append(utils.compute_flip(scored, pixels, flip_pixels_per_degree))
             pair = torch.stack(scores).cpu()                                  # the one read-back of the view: 8 bytes (12 with flip)
             psnr_values.append(float(pair[0]))
             ssim_values.append(float(pair[1]))
@@ -100,7 +156,7 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
         torch.cuda.synchronize(pred_color.device)
     seconds = time.perf_counter() - t0
     if save_output and not render_path:
-        write_metric_files(out_dir, step, psnr_values, ssim_values, flip_values if flip else None)
+        write_metric_files(out_dir, step, psnr_values, ssim_values, flip_values if flip else None, suffix)
     have = bool(psnr_values)
     res = {"psnrs": psnr_values, "ssims": ssim_values,
            "psnr": float(np.mean(np.array(psnr_values))) if have else None,
@@ -109,4 +165,6 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
     if flip:
         res["flips"] = flip_values
         res["flip"] = float(np.mean(np.array(flip_values))) if flip_values else None
+    if mask_mode is not None:
+        res["mask_mode"] = mask_mode
     return res
