@@ -38,7 +38,7 @@ extern "C" {
  * 4: the opt-in schedule fields no caller set are gone.  rnerf_train_cfg ends with aux_stream, grads_stream (nothing in between);
  * rnerf_prefetch ends with side_stream (the march always forks right before the last NerfMLP wgrad); rnerf_bkgd_backward is the only
  * background-MLP backward entry point.  Still 4 with rnerf_flip / rnerf_flip_workspace_bytes, rnerf_visual_hull_*, rnerf_marching_cubes_*,
- * rnerf_mesh_depth and rnerf_mask_dilate: they are appended, no existing entry point or struct moved. */
+ * rnerf_mesh_depth, rnerf_mask_dilate and rnerf_vis_*: they are appended, no existing entry point or struct moved. */
 #define RNERF_VERSION 4
 
 enum rnerf_status {
@@ -685,6 +685,58 @@ int rnerf_mesh_depth(const double* verts, int64_t num_verts, const int32_t* face
  *   rnerf_mask_dilate_workspace_bytes: H W rounded up to 16, + 16 ceil(H W / 256) (0 with a message for a bad size). */
 size_t rnerf_mask_dilate_workspace_bytes(int32_t height, int32_t width);
 int rnerf_mask_dilate(const uint8_t* mask, int32_t height, int32_t width, int32_t ky, int32_t kx, uint8_t* out, int32_t* bbox,
+                      void* workspace, void* stream);
+
+/* ---- Evaluation: depth visualisations.  Replaces vis.visualize_suite as eval.py:175 calls it (rnerf/vis.py; JAX, jax.scipy's
+ * convolve2d and matplotlib there).  Appended; RNERF_VERSION stays 4.  float32 per pixel in the order of the reference's formulas,
+ * eps = 2^-23; every reduction is a fixed-order fold of per-block partials and the sort uses integer histograms: no float atomics, the
+ * same inputs give the same bytes on every run.
+ *
+ * rnerf_vis_depth: visualize_depth (vis.py:45-111).  depth: float[H][W]; acc (nullable = all ones): float[H][W]; acc' = acc, 0 where
+ * depth is NaN (:75).  near, far: NaN = automatic (the reference's `near or ...` also takes 0 as automatic; the caller maps it), else
+ * rounded to float32.  Automatic bounds (:79-91): the pixels ordered by depth ascending, equal depths (-0 = +0) by pixel index, NaN last
+ * (jnp.argsort); cum = the inclusive running sum of acc' in that order, total = its end; kept iff cum >= total * ignore_frac and
+ * cum <= total * (1 - ignore_frac); near = the first kept depth - eps, far = the last kept depth + eps; both NaN when nothing is kept
+ * (the reference raises there).  ignore_frac == 0 keeps every pixel and sorts nothing: one reduction, near = the minimum - eps (NaN when
+ * every depth is NaN), far = the maximum + eps, or NaN if any depth is NaN.  ignore_frac > 0: a stable LSD radix sort of (key, pixel
+ * index), four 8-bit passes of per-block histogram and scatter by in-block rank, then cum in fp64: (the sum of the earlier blocks' sums
+ * + the earlier threads' sums) + the thread's own elements one by one, total = the sum of the blocks' sums, the two products and the
+ * comparisons in fp64.  Nothing is ordered when both bounds are given.
+ * curve (enum rnerf_vis_curve) is applied to depth, near and far (:94); the default of the reference is NEG_LOG.
+ * modulus > 0 (:97-99): value = floored_mod(d, modulus) / modulus (jnp.mod: the sign of the divisor), colour = sinebow(value) (:23-26),
+ * sin(pi x)^2 at 3/6 - v, 5/6 - v, 7/6 - v; NaN stays NaN.  modulus == 0 (:101-104): value = nan_to_num(clip((d - min(n, f)) / |f - n|,
+ * 0, 1)), min propagating NaN, NaN -> 0; colour = matplotlib's `turbo`, a list of 256 colours (csrc/turbo_table.h), entry
+ * min(int(value * 256), 255), not interpolated.  rgb = colour * acc' + (1 - acc') (:109).
+ * Outputs, each nullable but not all: rgb float[H][W][3]; value float[H][W], the scalar before the colour map; range device float[2] =
+ * (near, far) before the curve.
+ *   rnerf_vis_depth_workspace_bytes: 4 KiB, and with ignore_frac > 0 another 16 H W + O(H W / 4) bytes (0 with a message for a bad size
+ *   or ignore_frac).  The workspace (16-byte aligned) may be null when both bounds are given.
+ *
+ * rnerf_vis_normals: visualize_normals over depth_to_normals (vis.py:34-42, 114-132).  scaling: NaN = automatic (:116-122), over the
+ * pixels whose depth is not NaN: sqrt(((var x + var y) / 2) / var depth), population variances of the column index, the row index and the
+ * depth, each the fp64 sum of squared deviations from the fp64 mean (two passes of per-block partials), rounded to float32 once; equal
+ * depths give +inf.  z = scaling * depth; dy = convolve2d(z, [-1, 0, 1]^T / 2 (x) [1, 2, 1] / 4, mode='same'), dx with the transposed
+ * kernel: true convolutions, out[r][c] = sum over (p, q) of k[p][q] z[r + 1 - p][c + 1 - q] in that order from 0, zero outside the
+ * image, all nine products formed — a NaN pixel makes dx and dy NaN in its 3 x 3 neighbourhood.  inv = 1 / sqrt((1 + dx^2) + dy^2),
+ * normals = (dx inv, dy inv, inv).  rgb = isnan(normals) + nan_to_num((normals + 1) / 2), blended with the raw acc when acc is not null
+ * (not zeroed at a NaN depth, as there).  Outputs, each nullable but not both: rgb float[H][W][3]; normals float[H][W][3], the vectors
+ * before the colour step (what depth_to_normals returns, with scaling 1).
+ *   rnerf_vis_normals_workspace_bytes: 16 KiB (0 with a message for a bad size); may be null when scaling is given.
+ *
+ * Both: RNERF_ERR_ARG before any device work for null required pointers, H or W < 1, H * W >= 2^31, ignore_frac outside [0, 0.5) or not
+ * finite, modulus negative or not finite, an unknown curve, a workspace that is needed and null or not 16-byte aligned, an output that
+ * overlaps an input or another output. */
+enum rnerf_vis_curve {
+  RNERF_VIS_CURVE_NEG_LOG = 0,      /* -log(x + eps) */
+  RNERF_VIS_CURVE_IDENTITY = 1,
+  RNERF_VIS_CURVE_RECIPROCAL = 2,   /* 1 / (x + eps) */
+  RNERF_VIS_CURVE_LOG = 3           /* log(x + eps) */
+};
+size_t rnerf_vis_depth_workspace_bytes(int32_t height, int32_t width, double ignore_frac);
+int rnerf_vis_depth(const float* depth, const float* acc, int32_t height, int32_t width, double near, double far, double ignore_frac,
+                    int32_t curve, double modulus, float* rgb, float* value, float* range, void* workspace, void* stream);
+size_t rnerf_vis_normals_workspace_bytes(int32_t height, int32_t width);
+int rnerf_vis_normals(const float* depth, const float* acc, int32_t height, int32_t width, double scaling, float* rgb, float* normals,
                       void* workspace, void* stream);
 
 #ifdef __cplusplus

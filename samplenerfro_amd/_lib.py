@@ -34,6 +34,7 @@ class RnerfError(RuntimeError):
 
 
 TABLE_LAYOUTS = {"reference": 0, "bricks": 1}      # enum rnerf_table_layout
+VIS_CURVES = {"neg_log": 0, "identity": 1, "reciprocal": 2, "log": 3}      # enum rnerf_vis_curve
 
 
 class Grid(C.Structure):
@@ -174,6 +175,11 @@ SIGNATURES = {
     "rnerf_mesh_depth": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _i32, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rnerf_mask_dilate_workspace_bytes": (C.c_size_t, [_i32, _i32]),
     "rnerf_mask_dilate": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    # depth visualisations (csrc/vis.hip)
+    "rnerf_vis_depth_workspace_bytes": (C.c_size_t, [_i32, _i32, _dbl]),
+    "rnerf_vis_depth": (C.c_int, [_vp, _vp, _i32, _i32, _dbl, _dbl, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    "rnerf_vis_normals_workspace_bytes": (C.c_size_t, [_i32, _i32]),
+    "rnerf_vis_normals": (C.c_int, [_vp, _vp, _i32, _i32, _dbl, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -5,7 +5,8 @@ with utils.render_image (pipelined form), scores it on the device — PSNR of th
 (utils.compute_ssim, rnerf_ssim) — and reads back two floats per view.  With save_output it writes the reference's files.  With flip=True
 each view is also scored with LDR-FLIP (utils.compute_flip, rnerf_flip; metric/summary.py:72-78) and the read-back carries three floats.
 With masks / mask_mode the views are scored on the object's region and / or the crop around it (summary.py:91-92,177-205,
-metric/compare.py:132-133,167-197; the masks come from mesh_mask.render_masks).
+metric/compare.py:132-133,167-197; the masks come from mesh_mask.render_masks).  With vis_suite the depth visualisations of
+eval.py:175,196-198 (vis.visualize_suite: rnerf_vis_depth, rnerf_vis_normals) are computed for every view and written with save_output.
 """
 from __future__ import annotations
 
@@ -91,7 +92,7 @@ def apply_mask(pred_color: torch.Tensor, pixels: torch.Tensor, mask, mask_mode: 
 
 def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192, normalize_disp: bool = False, out_dir: Optional[str] = None,
              step=None, save_output: bool = False, render_path: bool = False, flip: bool = False,
-             flip_pixels_per_degree: Optional[float] = None, masks=None, mask_mode: Optional[str] = None) -> dict:
+             flip_pixels_per_degree: Optional[float] = None, masks=None, mask_mode: Optional[str] = None, vis_suite: bool = False) -> dict:
     """Render and score every view (eval.py:155-215).
 
     model / variables: what models.construct_nerf returns; views: batches as device_views yields them; rng: the render key (eval.py passes
@@ -112,7 +113,11 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
     over every pixel of the (cropped) image as there, not normalised by the mask's area.  The metric files carry mask_suffix(mask_mode)
     before ".txt" — "_mask" for "mask" AND for "mask_crop", "_crop" for "crop": summary.py:165's `"_mask" if MASK else "" + "_crop" if
     CROP else ""` parses that way.  The PNGs are written unmasked.  The result gains "mask_mode".  A crop smaller than the SSIM window
-    is a ValueError, and so is masks without mask_mode or the reverse; with neither, nothing changes."""
+    is a ValueError, and so is masks without mask_mode or the reverse; with neither, nothing changes.
+
+    vis_suite=True computes vis.visualize_suite(pred_disp[..., 0], pred_acc[..., 0]) for every view (eval.py:175; seven more launches, no
+    read-back); with save_output it also writes depth_{idx:03d}.png, depth_mod_{idx:03d}.png and depth_normals_{idx:03d}.png
+    (eval.py:196-198) through utils.save_img.  With vis_suite=False the keys, the files and the launches are those of the loop without it."""
     if (masks is None) != (mask_mode is None):
         raise ValueError("evaluate: masks and mask_mode go together (got only one of them)")
     suffix = mask_suffix(mask_mode)
@@ -152,6 +157,12 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
         if save_output:
             utils.save_img(pred_color, os.path.join(out_dir, "{:03d}.png".format(idx)))
             utils.save_img(pred_disp[..., 0], os.path.join(out_dir, "disp_{:03d}.png".format(idx)))
+        if vis_suite:
+            from . import vis
+            suite = vis.visualize_suite(pred_disp[..., 0], _pred_acc[..., 0])
+            if save_output:
+                for name in ("depth", "depth_mod", "depth_normals"):
+                    utils.save_img(suite[name], os.path.join(out_dir, "{}_{:03d}.png".format(name, idx)))
     if num_rays:
         torch.cuda.synchronize(pred_color.device)
     seconds = time.perf_counter() - t0

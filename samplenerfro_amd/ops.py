@@ -698,3 +698,75 @@ def flip(reference: torch.Tensor, test: torch.Tensor, *, pixels_per_degree: floa
         mean = None if return_map else torch.empty(tuple(lead), dtype=torch.float32, device=dev)
         check(lib.rnerf_flip(ptr(a), ptr(b), n, H, W, ppd, ptr(out_map), ptr(mean), ptr(ws), stream), "rnerf_flip")
     return out_map if return_map else mean
+
+
+def _vis_plane(t, name: str) -> torch.Tensor:
+    if t.dim() != 2 or int(t.shape[0]) < 1 or int(t.shape[1]) < 1:
+        raise ValueError(f"{name}: need a non-empty [H, W] plane, got shape {tuple(t.shape)}")
+    return _chk(t, name)
+
+
+def vis_depth(depth: torch.Tensor, acc: Optional[torch.Tensor] = None, *, near: Optional[float] = None, far: Optional[float] = None,
+              ignore_frac: float = 0.0, curve: str = "neg_log", modulus: float = 0.0, want_rgb: bool = True, want_value: bool = False,
+              want_range: bool = False):
+    """visualize_depth (rnerf/vis.py:45-111) on the device (rnerf_vis_depth).  depth, acc (None = all ones): float32 device tensors
+    [H, W]; near / far: None = automatic.  -> (rgb [H, W, 3], value [H, W], range [2] = (near, far) before the curve), None for what was
+    not wanted.  Issued on the current stream of depth's device; nothing is synchronised."""
+    d = _vis_plane(depth, "depth")
+    H, W = int(d.shape[0]), int(d.shape[1])
+    a = None
+    if acc is not None:
+        a = _vis_plane(acc, "acc")
+        if tuple(a.shape) != (H, W) or a.device != d.device:
+            raise ValueError(f"vis_depth: acc {tuple(a.shape)} on {a.device} does not match depth {(H, W)} on {d.device}")
+    if curve not in _lib.VIS_CURVES:
+        raise ValueError(f"vis_depth: curve must be one of {sorted(_lib.VIS_CURVES)}, got {curve!r}")
+    if not (want_rgb or want_value or want_range):
+        raise ValueError("vis_depth: nothing wanted")
+    nan = float("nan")
+    n, f, frac = nan if near is None else float(near), nan if far is None else float(far), float(ignore_frac)
+    lib = _lib.load()
+    dev = d.device
+    with torch.cuda.device(dev):
+        ws = None
+        if n != n or f != f:
+            nb = lib.rnerf_vis_depth_workspace_bytes(H, W, frac)
+            if nb == 0:
+                check(-1, "rnerf_vis_depth_workspace_bytes")
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        rgb = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if want_rgb else None
+        value = torch.empty((H, W), dtype=torch.float32, device=dev) if want_value else None
+        rng = torch.empty(2, dtype=torch.float32, device=dev) if want_range else None
+        check(lib.rnerf_vis_depth(ptr(d), ptr(a), H, W, n, f, frac, _lib.VIS_CURVES[curve], float(modulus), ptr(rgb), ptr(value), ptr(rng), ptr(ws),
+                                  torch.cuda.current_stream(dev).cuda_stream), "rnerf_vis_depth")
+    return rgb, value, rng
+
+
+def vis_normals(depth: torch.Tensor, acc: Optional[torch.Tensor] = None, *, scaling: Optional[float] = None, want_rgb: bool = True,
+                want_normals: bool = False):
+    """visualize_normals / depth_to_normals (rnerf/vis.py:34-42, 114-132) on the device (rnerf_vis_normals).  depth, acc (None = no
+    blend): float32 device tensors [H, W]; scaling: None = automatic.  -> (rgb [H, W, 3], normals [H, W, 3]), None for what was not
+    wanted.  Issued on the current stream of depth's device; nothing is synchronised."""
+    d = _vis_plane(depth, "depth")
+    H, W = int(d.shape[0]), int(d.shape[1])
+    a = None
+    if acc is not None:
+        a = _vis_plane(acc, "acc")
+        if tuple(a.shape) != (H, W) or a.device != d.device:
+            raise ValueError(f"vis_normals: acc {tuple(a.shape)} on {a.device} does not match depth {(H, W)} on {d.device}")
+    if not (want_rgb or want_normals):
+        raise ValueError("vis_normals: nothing wanted")
+    lib = _lib.load()
+    dev = d.device
+    with torch.cuda.device(dev):
+        ws = None
+        if scaling is None:
+            nb = lib.rnerf_vis_normals_workspace_bytes(H, W)
+            if nb == 0:
+                check(-1, "rnerf_vis_normals_workspace_bytes")
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        rgb = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if want_rgb else None
+        normals = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if want_normals else None
+        check(lib.rnerf_vis_normals(ptr(d), ptr(a), H, W, float("nan") if scaling is None else float(scaling), ptr(rgb), ptr(normals), ptr(ws),
+                                    torch.cuda.current_stream(dev).cuda_stream), "rnerf_vis_normals")
+    return rgb, normals
