@@ -739,6 +739,20 @@ size_t rnerf_vis_normals_workspace_bytes(int32_t height, int32_t width);
 int rnerf_vis_normals(const float* depth, const float* acc, int32_t height, int32_t width, double scaling, float* rgb, float* normals,
                       void* workspace, void* stream);
 
+/* ---- scene images (csrc/images.hip) ------------------------------------------------------------------------------------------------
+ * rnerf_images_prepare: the pixel arithmetic of Blender / NSVF / OpenCV._load_renderings (rnerf/datasets.py:348-364, :394-414, :443-459)
+ * on the decoded 8-bit views.  src: device uint8 [n][H][W][C], C = 3 (RGB) or 4 (RGBA, 4-byte aligned); dst: device float
+ * [n][H / factor][W / factor][3].  Every operation is one correctly rounded float32 operation:
+ *   factor 1: x = float(u) / 255.
+ *   factor 2: x = float(u00 + u01 + u10 + u11) / 1020 per channel, alpha included: the mean of each 2 x 2 block from its exact integer
+ *             sum (the reference averages four float32 u / 255 with cv2.INTER_AREA: at most 2^-22 away).  H, W even.
+ *   white_bkgd (needs C == 4): out_c = x_c * x_a + (1 - x_a) on those values (:359-362); otherwise the first three channels.
+ * One thread per output pixel, nothing allocated, no workspace.  RNERF_ERR_ARG before any device work for null pointers, C not 3 or 4,
+ * factor not 1 or 2, odd H or W at factor 2, white_bkgd not 0 or 1 or set with C == 3, n, H or W < 1, 2^39 output pixels or more, a
+ * misaligned pointer. */
+int rnerf_images_prepare(const uint8_t* src, int64_t n, int32_t H, int32_t W, int32_t C, int32_t factor, int32_t white_bkgd, float* dst,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -180,6 +180,8 @@ SIGNATURES = {
     "rnerf_vis_depth": (C.c_int, [_vp, _vp, _i32, _i32, _dbl, _dbl, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
     "rnerf_vis_normals_workspace_bytes": (C.c_size_t, [_i32, _i32]),
     "rnerf_vis_normals": (C.c_int, [_vp, _vp, _i32, _i32, _dbl, _vp, _vp, _vp, _vp]),
+    # scene images (csrc/images.hip)
+    "rnerf_images_prepare": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -770,3 +770,24 @@ def vis_normals(depth: torch.Tensor, acc: Optional[torch.Tensor] = None, *, scal
         check(lib.rnerf_vis_normals(ptr(d), ptr(a), H, W, float("nan") if scaling is None else float(scaling), ptr(rgb), ptr(normals), ptr(ws),
                                     torch.cuda.current_stream(dev).cuda_stream), "rnerf_vis_normals")
     return rgb, normals
+
+
+def images_prepare(u8: torch.Tensor, factor: int = 1, white_bkgd: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The pixel arithmetic of the reference's loaders (rnerf/datasets.py:348-364) on the device (rnerf_images_prepare): decoded views, uint8
+    [n, H, W, C] with C = 3 or 4, -> float32 [n, H / factor, W / factor, 3]: u / 255 (factor 1) or the 2 x 2 block sum / 1020 (factor 2,
+    the reference's INTER_AREA halving), composited over white with white_bkgd (needs the alpha channel), else the first three channels.
+    out: a contiguous float32 tensor of that shape to write into (a slice of the scene's tensor)."""
+    lib = _lib.load()
+    src = _chk(u8, "images", torch.uint8)
+    if src.dim() != 4:
+        raise ValueError("images_prepare: images must be [n, H, W, C]")
+    n, H, W, ch = (int(v) for v in src.shape)
+    factor = int(factor)
+    shape = (n, H // factor, W // factor, 3) if factor in (1, 2) else (n, H, W, 3)      # a bad factor is the library's error
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != src.device or not out.is_contiguous():
+        raise ValueError(f"images_prepare: out must be a contiguous float32 tensor of shape {shape} on {src.device}")
+    check(lib.rnerf_images_prepare(ptr(src), n, H, W, ch, factor, int(bool(white_bkgd)), ptr(out), torch.cuda.current_stream(src.device).cuda_stream),
+          "rnerf_images_prepare")
+    return out

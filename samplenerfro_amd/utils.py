@@ -55,6 +55,9 @@ def default_flags(**overrides) -> types.SimpleNamespace:
         grad_max_val=0.0, max_steps=1000000, num_path_samples=8, sparsity_weight=0.0, use_fine_sparsity=False,
         use_online_sparsity=True, normal_loss_weight=0.0, normal_smooth_weight=0.0, beta_weight=0.0, bg_weight=0.0,
         bg_smooth_weight=0.0, bg_patch_size=0, chunk=8192,
+        # the scene (datasets.get_dataset); factor 4 makes the Blender loader raise, as in the reference: every shipped config sets it
+        dataset="blender", data_dir=None, factor=4, skip_frames=1, eval_train=False, render_path=False, use_pixel_centers=False,
+        precrop_iters=0, precrop_frac=0.5, batching="single_image",
         backward_precision="f16x3",      # not a reference flag: arithmetic of the HIP backward (train.backward_mode)
         range_retry="lag",               # not a reference flag: re-run a step whose f16-based arithmetic left its range (train.train_step):
                                          # "lag" = decided two steps later (no per-step host read), True = in place (one read per step), False = never
