@@ -4,6 +4,7 @@
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -15,7 +16,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "librnerf.so")
 LIB_EXPERIMENTS = os.path.join(LIBDIR, "librnerf_experiments.so")
 LIB_UBENCH = os.path.join(LIBDIR, "librnerf_ubench.so")       # csrc/ubench/mfma_rate.hip: the measured MFMA ceiling bench.py quotes (not the product)
-SOURCES = ["grid.hip", "march.hip", "render.hip", "mlp.hip", "mlp_f32.hip", "bkgd16.hip", "pipeline.hip", "metrics.hip", "hull.hip", "mcubes.hip", "raster.hip", "vis.hip", "images.hip"]
+SOURCES = ["grid.hip", "march.hip", "render.hip", "mlp.hip", "small_mlp.hip", "mlp_f32.hip", "bkgd16.hip", "pipeline.hip", "metrics.hip", "hull.hip", "mcubes.hip", "raster.hip", "vis.hip", "images.hip"]
 # -ffp-contract=off + correctly rounded div/sqrt: the march/lookup/resample kernels reproduce the reference's
 # individually rounded fp32 op order so that integer indices are bit-exact against the oracle.
 # -fno-slp-vectorize: a performance choice first — hipcc's SLP pass packs adjacent scalar fp32 ops into v_pk_{mul,add,fma}_f32, which beside
@@ -58,10 +59,7 @@ def build(force: bool = False, verbose: bool = False, experiments: bool = True) 
     from concurrent.futures import ThreadPoolExecutor
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(HERE, "..", "include", "rnerf.h"),
-               os.path.join(CSRC, "ior_train_kernels.inc"), os.path.join(CSRC, "ior_train_api.inc"), os.path.join(CSRC, "nerfmlp_layout.h"),
-               os.path.join(CSRC, "mfma_ops.h"), os.path.join(CSRC, "bkgd_layout.h"), os.path.join(CSRC, "so3_layout.h"), os.path.join(CSRC, "mc_tables.h"),
-               os.path.join(CSRC, "turbo_table.h")]
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "rnerf.h")]
     variants = [(LIB, LIBDIR, [])]
     if experiments:
         variants.append((LIB_EXPERIMENTS, os.path.join(LIBDIR, "exp"), ["-DRNERF_EXPERIMENTS"]))
@@ -77,7 +75,7 @@ def build(force: bool = False, verbose: bool = False, experiments: bool = True) 
                 jobs.append(([hipcc] + FLAGS + extra + ["-c", s, "-o", o], verbose))
         links.append((lib, objs))
     if jobs:
-        # longest first (mlp.hip takes ~2 min, the rest seconds): the two mlp.o builds run side by side
+        # longest first (mlp.hip takes ~1.5 min, small_mlp.hip ~5 s, the rest seconds): the two mlp.o builds run side by side
         jobs.sort(key=lambda j: -os.path.getsize(j[0][-3]))
         with ThreadPoolExecutor(max_workers=min(len(jobs), max(2, (os.cpu_count() or 2) // 2))) as ex:
             list(ex.map(_compile, jobs))

@@ -1,6 +1,6 @@
 // The background MLP on the f16 matrix cores (round 4): forward (inference / training) of MLP(128, 4, skip 2, out 3) on pos_enc(dir, 0, 4)
 // + the rgb activation.  Reference: rnerf/models.py:181-191 (forward_envmap), :303, :336-337; rnerf/model_utils.py:93-140 (MLP), :187-214.
-// The backward kernels of the same network (exact fp32 MFMA) live in csrc/mlp.hip.
+// The backward kernels of the same network (exact fp32 MFMA) live in csrc/small_mlp.hip.
 #include "mfma_ops.h"
 #include "bkgd_layout.h"
 #include "so3_layout.h"
@@ -210,8 +210,8 @@ __global__ void __launch_bounds__(64) bkgd16_fwd_kernel(const float* __restrict_
   }
 }
 
-int launch_bkgd16_fwd(bool train, const float* params, const float* dirs, int dir_stride, long long n, float pad_scale, float pad, float* out_rgb,
-                      float* save, hipStream_t st) {
+static int launch_bkgd16_fwd(bool train, const float* params, const float* dirs, int dir_stride, long long n, float pad_scale, float pad, float* out_rgb,
+                             float* save, hipStream_t st) {
   const dim3 grid((unsigned)((n + 31) / 32));
   if (train) hipLaunchKernelGGL(bkgd16_fwd_kernel<true>, grid, dim3(64), 0, st, params, dirs, dir_stride, n, pad_scale, pad, out_rgb, save);
   else hipLaunchKernelGGL(bkgd16_fwd_kernel<false>, grid, dim3(64), 0, st, params, dirs, dir_stride, n, pad_scale, pad, out_rgb, save);
@@ -223,7 +223,7 @@ int launch_bkgd16_fwd(bool train, const float* params, const float* dirs, int di
 // MLP(128, 4, skip 2, out 3) on the 60 windowed encoding features (rnerf/ior_utils.py:148-152, rnerf/model_utils.py:236-245): lane half h
 // holds feature 2 p + h in enc[p] (so3_encode), i.e. four k-steps of 8 slots with p = 8 s + j, slot p = 30 free for the bias.  The prev-layer
 // blocks are the background MLP's (same [128][128] kernels, same slot map).  Saved tensors: the fp32 layout of csrc/so3_layout.h, which the backward
-// kernels of csrc/ior_train_kernels.inc read.
+// kernels of csrc/small_mlp.hip read.
 template <bool FIRST>
 __device__ __forceinline__ void so3_16_enc_layer(f32x16 (&acc)[4], const float (&enc)[30], const float* __restrict__ pe, const Bkgd16Lane& L, int koff, int boff) {
   bkgd16_layer<4, FIRST>(acc,
@@ -298,10 +298,35 @@ __global__ void __launch_bounds__(64) so3_16_fwd_train_kernel(const float* __res
   if (ok && h == 0) *(float4*)(save + (size_t)n * (60 + 4 * 128) + (size_t)row * 4) = make_float4(o[0], o[1], o[2], 0.f);
 }
 
-int launch_so3_16_fwd_train(const float* params, So3Window win, const float* pts4, long long n, float* save, hipStream_t st) {
+static int launch_so3_16_fwd_train(const float* params, So3Window win, const float* pts4, long long n, float* save, hipStream_t st) {
   hipLaunchKernelGGL(so3_16_fwd_train_kernel, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, st, params, win, (const float4*)pts4, n, save);
   RNERF_CHECK_LAUNCH();
   return RNERF_OK;
 }
 
 }  // namespace rnerf
+
+using namespace rnerf;
+
+extern "C" int rnerf_bkgd_forward(const float* params, const float* dirs, int32_t dir_stride, int64_t n, double rgb_padding,
+                                  float* out_rgb, void* stream) {
+  RNERF_CHECK_ARG(params && dirs && out_rgb, "rnerf_bkgd_forward: null pointer");
+  RNERF_CHECK_ARG(dir_stride >= 3, "rnerf_bkgd_forward: dir_stride must be >= 3");
+  RNERF_CHECK_ARG(n >= 1, "rnerf_bkgd_forward: n must be >= 1");
+  return launch_bkgd16_fwd(false, params, dirs, dir_stride, (long long)n, (float)(1 + 2 * rgb_padding), (float)rgb_padding, out_rgb, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int rnerf_bkgd_forward_train(const float* params, const float* dirs, int32_t dir_stride, int64_t n, double rgb_padding,
+                                        float* out_rgb, void* save, void* stream) {
+  RNERF_CHECK_ARG(params && dirs && out_rgb && save, "rnerf_bkgd_forward_train: null pointer");
+  RNERF_CHECK_ARG(dir_stride >= 3 && n >= 1, "rnerf_bkgd_forward_train: need dir_stride >= 3 and n >= 1");
+  return launch_bkgd16_fwd(true, params, dirs, dir_stride, (long long)n, (float)(1 + 2 * rgb_padding), (float)rgb_padding, out_rgb, (float*)save, (hipStream_t)stream);
+}
+
+extern "C" int rnerf_so3_forward_train(const float* so3_params, const float* window10, const float* pts4, int64_t n, void* save, void* stream) {
+  RNERF_CHECK_ARG(so3_params && window10 && pts4 && save, "rnerf_so3_forward_train: null pointer");
+  RNERF_CHECK_ARG(n >= 1, "rnerf_so3_forward_train: n must be >= 1");
+  So3Window w;
+  for (int i = 0; i < 10; ++i) w.w[i] = window10[i];
+  return launch_so3_16_fwd_train(so3_params, w, pts4, (long long)n, (float*)save, (hipStream_t)stream);
+}

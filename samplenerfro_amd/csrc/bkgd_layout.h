@@ -1,5 +1,5 @@
 // Background MLP (rnerf/models.py:181-191: MLP(128, 4, skip 2, out 3) on pos_enc(dir, 0, 4)): parameter / saved-tensor layouts shared by the
-// exact-fp32 kernels (csrc/mlp.hip) and the f16 hi + lo ones (csrc/bkgd16.hip).
+// exact-fp32 kernels (csrc/small_mlp.hip) and the f16 hi + lo ones (csrc/bkgd16.hip).
 #pragma once
 #include "nerfmlp_layout.h"
 
@@ -24,9 +24,5 @@ __host__ __device__ constexpr int dir_feature(int q, int h) { return q < 12 ? (h
 __host__ __device__ constexpr size_t bkgd_save_floats(long long n) { return (size_t)n * (28 + 4 * 128 + 3); }
 // scratch: [dY0..dY3: n x 128][d raw: n x 4, padded to n x 128 so that dY_k = base + k*n*128][wgrad partials: chunks x params]
 __host__ __device__ constexpr size_t bkgd_dy_floats(long long n) { return (size_t)n * (5 * 128) + (size_t)((n + 255) / 256) * RNERF_BKGDMLP_PARAMS; }
-
-// csrc/bkgd16.hip
-int launch_bkgd16_fwd(bool train, const float* params, const float* dirs, int dir_stride, long long n, float pad_scale, float pad, float* out_rgb,
-                      float* save, hipStream_t st);
 
 }  // namespace rnerf

@@ -231,7 +231,7 @@ __device__ __forceinline__ float quad_sumsq3(float a) {
   return fadd(fadd(quad_bcast<0>(a2), quad_bcast<1>(a2)), quad_bcast<2>(a2));
 }
 
-// The marching waves (march.hip, march_all_kernel in mlp.hip) are bound by instruction issue, so its integer glue is written as the instructions the ISA has for it (hipcc emits 3-4 for
+// The marching waves (march.hip, march_all_kernel in small_mlp.hip) are bound by instruction issue, so its integer glue is written as the instructions the ISA has for it (hipcc emits 3-4 for
 // each): clamp to [0, hi] = the median of (v, 0, hi); floor + convert in one; a*(1-t) + b*t with both products in one packed multiply
 // (v_pk_mul_f32 rounds each half like v_mul_f32: the same individually rounded ops in the same order).
 __device__ __forceinline__ int clamp0(int v, int hi) {

@@ -1,4 +1,4 @@
-// Shared pieces of the matrix-core kernels (csrc/mlp.hip: NerfMLP engines; csrc/bkgd16.hip: the background MLP on f16 hi + lo operands):
+// Shared pieces of the matrix-core kernels (csrc/mlp.hip: NerfMLP engines; csrc/small_mlp.hip: the small MLPs in exact fp32; csrc/bkgd16.hip: the same on f16 hi + lo operands):
 // vector types, the 16-bit hi / lo split, the 32x32x16 MFMA wrapper and the operand-slot -> feature maps of the transposed chain
 // (lane (row m = lane & 31, half h = lane >> 5) of an accumulator holds features n = 32 t + (r & 3) + 8 (r >> 2) + 4 h — see mlp.hip).
 #pragma once

@@ -1,5 +1,5 @@
 // so3_mlp (rnerf/ior_utils.py:148-152: MLP(128, 4, skip 2, out 3) on annealed_pos_enc(x)): parameter / saved-tensor layouts and the windowed
-// encoding, shared by the exact-fp32 kernels (csrc/mlp.hip, csrc/ior_train_kernels.inc) and the f16 hi + lo training forward (csrc/bkgd16.hip).
+// encoding, shared by the exact-fp32 kernels (csrc/small_mlp.hip) and the f16 hi + lo training forward (csrc/bkgd16.hip).
 #pragma once
 #include "nerfmlp_layout.h"
 
@@ -61,8 +61,5 @@ __device__ __forceinline__ void so3_store_mask(float* save, long long n, long lo
 __device__ __forceinline__ uint4 so3_load_mask(const float* save, long long n, long long row, int k) {
   return *(const uint4*)((const uint32_t*)(save + so3_save_floats(n)) + ((size_t)(k - 1) * (size_t)n + (size_t)row) * 4);
 }
-
-// csrc/bkgd16.hip: the training forward on f16 hi + lo MFMAs (same saved layout)
-int launch_so3_16_fwd_train(const float* params, So3Window win, const float* pts4, long long n, float* save, hipStream_t st);
 
 }  // namespace rnerf

@@ -228,7 +228,7 @@ def _ior_stage_step(model: NerfModel, rng, state: TrainState, batch, flags):
 
 
 def _all_stage_backward(model: NerfModel, state: TrainState, variables, ctx, dy_c, d_bk_dirs, bwd: int, annealed: float, taps) -> None:
-    """Stage all*: d loss / d so3_mlp through the marched path (csrc/ior_train_kernels.inc).  Only the coarse level and the background
+    """Stage all*: d loss / d so3_mlp through the marched path (csrc/small_mlp.hip).  Only the coarse level and the background
     colour reach the path: sample_pdf stops the gradient of everything it returns (rnerf/model_utils.py:406-411), ray_dist is
     stop_gradient'ed (eikonal_utils.py:121), and |ray_dir| = 1 makes the compositing's delta independent of the direction."""
     B, Nc, N = ctx["B"], model.num_coarse_samples, model.num_samples

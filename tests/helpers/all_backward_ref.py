@@ -1,4 +1,4 @@
-"""References for the five stage-"all*" backward kernels (csrc/ior_train_kernels.inc), in torch on the CPU (TEST INFRASTRUCTURE, no device).
+"""References for the five stage-"all*" backward kernels (csrc/small_mlp.hip; the input gradient: csrc/mlp.hip), in torch on the CPU (TEST INFRASTRUCTURE, no device).
 
 Each reference states ONE kernel's operation, on the inputs that kernel was given, from the pieces of oracle/torch_ref.py and torch.autograd —
 none repeats the kernels' hand-derived formulas.  Every function computes in the dtype of its tensor arguments: float64 is the reference,

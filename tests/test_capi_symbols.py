@@ -44,6 +44,15 @@ def test_binding_covers_header(lib_path):
     assert b"precision" in lib.rnerf_last_error()
 
 
+def test_every_translation_unit_is_in_the_library():
+    """build.SOURCES is exactly csrc/*.hip, and no text is spliced into one of them from a csrc/*.inc."""
+    from samplenerfro_amd import build
+    names = os.listdir(os.path.join(ROOT, "samplenerfro_amd", "csrc"))
+    assert len(build.SOURCES) == len(set(build.SOURCES))
+    assert set(build.SOURCES) == {n for n in names if n.endswith(".hip")}
+    assert not [n for n in names if n.endswith(".inc")]
+
+
 def test_missing_library_fails_loudly(tmp_path):
     import pytest
     with pytest.raises(_lib.RnerfError):

@@ -1,4 +1,4 @@
-"""The five kernels of csrc/ior_train_kernels.inc that carry so3_mlp's gradient through the march's adjoint (so3 dgrad + wgrad,
+"""The five kernels of csrc/small_mlp.hip and csrc/mlp.hip that carry so3_mlp's gradient through the march's adjoint (so3 dgrad + wgrad,
 so3_pair_jacobian, march_adjoint, nerfmlp_input_grad<1|2|3>), each called through its ops.* wrapper and compared with a float64 reference of
 that ONE operation evaluated at the inputs the kernel was given (tests/helpers/all_backward_ref.py, proven by
 tests/test_all_backward_ref_host.py) — on a NON-cubic grid with unequal extents, in both table layouts, at every tail length of the scan's

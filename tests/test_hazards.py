@@ -2,8 +2,8 @@
 
 LLVM inserts the wait states gfx90a+ needs between a matrix instruction and a dependent VALU instruction only for instructions it knows
 to be VALU; the one-line `asm("v_...")` statements the kernels place in MFMA shadows are opaque to it.  Round 2 met wrong values in a few
-lanes, differently from run to run, in one schedule of the f16 dgrad kernel (SLP vectoriser on).  This test compiles csrc/mlp.hip with the
-product flags (hipcc cross-compiles, no GPU) and scans the emitted ISA for the two hazard patterns; tests/test_gpu_backward.py checks on
+lanes, differently from run to run, in one schedule of the f16 dgrad kernel (SLP vectoriser on).  This test compiles csrc/mlp.hip and
+csrc/small_mlp.hip with the product flags (hipcc cross-compiles, no GPU) and scans the emitted ISA for the two hazard patterns; tests/test_gpu_backward.py checks on
 the device that repeated runs of the backward kernels are bit-identical."""
 import os
 import sys
@@ -12,18 +12,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def test_no_mfma_inline_asm_hazards_in_the_product_build(tmp_path):
+def _scan(name):
+    """-> (MFMAs, inline-asm VALU statements, hazard candidates) in the product build of csrc/<name>"""
     import hazard_check as H
-    src = os.path.join(ROOT, "samplenerfro_amd", "csrc", "mlp.hip")
-    asm = H.compile_to_asm(src, [])
+    asm = H.compile_to_asm(os.path.join(ROOT, "samplenerfro_amd", "csrc", name), [])
     try:
         funcs = H.parse(asm)
     finally:
         os.unlink(asm)
     n_asm = sum(1 for c in funcs.values() for ins in c if ins[2] and ins[0].startswith("v_"))
     n_mfma = sum(1 for c in funcs.values() for ins in c if ins[0].startswith("v_mfma"))
+    return n_mfma, n_asm, H.check(funcs)
+
+
+def test_no_mfma_inline_asm_hazards_in_the_product_build(tmp_path):
+    n_mfma, n_asm, found = _scan("mlp.hip")
     assert n_mfma > 10000 and n_asm > 3000          # the scan saw the engines (forward, dgrad, wgrad) and their asm statements
-    found = H.check(funcs)
+    assert not found, found[:10]
+    n_mfma, n_asm, found = _scan("small_mlp.hip")
+    assert n_mfma > 2000                            # ... and the small-MLP / stage-"all" kernels
     assert not found, found[:10]
 
 

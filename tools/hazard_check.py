@@ -16,7 +16,7 @@ in the f16 dgrad kernel with the SLP vectoriser on; this tool checks every build
 Every instruction counts one wait state, `s_nop N` counts N + 1.  The scan is linear per function (basic-block order of the .s file, branch
 targets ignored): a conservative approximation, good for the straight-line MFMA loops these kernels consist of.
 
-usage: python tools/hazard_check.py [--flags "<extra hipcc flags>"] [file.hip ...]      (default: csrc/mlp.hip with the product flags)
+usage: python tools/hazard_check.py [--flags "<extra hipcc flags>"] [file.hip ...]      (default: csrc/mlp.hip and csrc/small_mlp.hip with the product flags)
 exit code 1 if a hazard is found.
 """
 import os
@@ -124,7 +124,7 @@ def main():
     if args and args[0] == "--flags":
         extra = args[1].split()
         args = args[2:]
-    srcs = args or [os.path.join(ROOT, "samplenerfro_amd", "csrc", "mlp.hip")]
+    srcs = args or [os.path.join(ROOT, "samplenerfro_amd", "csrc", f) for f in ("mlp.hip", "small_mlp.hip")]
     bad = 0
     for src in srcs:
         asm = src if src.endswith(".s") else compile_to_asm(src, extra)

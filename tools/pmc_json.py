@@ -26,7 +26,7 @@ except Exception:
     head = ""
 version = open(os.path.join(ROOT, "VERSION")).read().strip() if os.path.exists(os.path.join(ROOT, "VERSION")) else ""
 res = {"note": note, "bench_py_sha16": sha(os.path.join(ROOT, "bench.py")),
-       "csrc_sha16": {f: sha(os.path.join(CSRC, f)) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".inc", ".h"))},
+       "csrc_sha16": {f: sha(os.path.join(CSRC, f)) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h"))},
        "head": head or ("VERSION: " + version if version else "(snapshot without .git and without VERSION)"),
        "xcd_instances": 8,
        "units": "GRBM_GUI_ACTIVE / GRBM_COUNT are summed over the 8 XCDs' GRBM instances (divide by 8 for cycles); FETCH_SIZE / WRITE_SIZE in KiB as reported by rocprofv3 (gfx950: wide 16 B/lane reads are counted at half their size); SQ_* as reported "
