@@ -38,7 +38,8 @@ extern "C" {
  * 4: the opt-in schedule fields no caller set are gone.  rnerf_train_cfg ends with aux_stream, grads_stream (nothing in between);
  * rnerf_prefetch ends with side_stream (the march always forks right before the last NerfMLP wgrad); rnerf_bkgd_backward is the only
  * background-MLP backward entry point.  Still 4 with rnerf_flip / rnerf_flip_workspace_bytes, rnerf_visual_hull_*, rnerf_marching_cubes_*,
- * rnerf_mesh_depth, rnerf_mask_dilate and rnerf_vis_*: they are appended, no existing entry point or struct moved. */
+ * rnerf_mesh_depth, rnerf_mask_dilate, rnerf_vis_*, rnerf_images_prepare, rnerf_errmap_* and rnerf_ssim_summary: they are appended, no
+ * existing entry point or struct moved. */
 #define RNERF_VERSION 4
 
 enum rnerf_status {
@@ -752,6 +753,48 @@ int rnerf_vis_normals(const float* depth, const float* acc, int32_t height, int3
  * misaligned pointer. */
 int rnerf_images_prepare(const uint8_t* src, int64_t n, int32_t H, int32_t W, int32_t C, int32_t factor, int32_t white_bkgd, float* dst,
                          void* stream);
+
+/* ---- error maps and the comparison sheet of metric/summary.py (csrc/metrics.hip, csrc/errmap.hip) --------------------------------------
+ * Appended; RNERF_VERSION stays 4.  What summary.py writes per view besides its numbers: errmap/psnr_NNN.png, ssim_NNN.png, flip_NNN.png
+ * and errmap/frame/frame_NNN.png.  The FLIP map is rnerf_flip's `map`.  The LPIPS panel and column are not reproduced.
+ *
+ * rnerf_errmap_mse: compute_psnr's map and mean squared error (summary.py:49-54).  reference, test: float[n][H][W][C]; map (nullable):
+ * float[n][H][W], the mean over the channels of (reference - test)^2, every operation one rounded float32 operation, the channels added
+ * in order; mean (nullable, not both null): float[n], the mean of the float32 squares of each image (summary.py:51) as a fixed-order fp64
+ * sum of per-workgroup partials in `workspace` (rnerf_errmap_mse_workspace_bytes, 8-byte aligned; unused when mean is null): the same
+ * inputs give the same bits on every run.  RNERF_ERR_ARG before any device work for null pointers, n, H, W or C < 1, more than 2^31
+ * workgroups of 256 pixels, a map that overlaps an input. */
+size_t rnerf_errmap_mse_workspace_bytes(int64_t n, int32_t H, int32_t W);
+int rnerf_errmap_mse(const float* reference, const float* test, int64_t n, int32_t H, int32_t W, int32_t C, float* map, float* mean,
+                     void* workspace, void* stream);
+
+/* rnerf_ssim_summary: metric/ssim/ssim.py:45-133 (the pytorch-msssim formula) as summary.py:56-61,115 calls it — not rnerf_ssim's
+ * formula.  img0, img1: float[n][H][W][C].  The Gaussian window (_fspecial_gauss_1d, :20-24; summary.py uses filter_size 11,
+ * filter_sigma 1.5) is computed on the host in double and rounded to float once; "valid" convolution; C1 = (0.01 data_range)^2,
+ * C2 = (0.03 data_range)^2 (summary.py: data_range 1);
+ *   ssim = ((2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1)) * ((2 sigma12 + C2) / (sigma1^2 + sigma2^2 + C2)), nothing clamped.
+ * map (nullable): float[n][H-fs+1][W-fs+1], the mean over the channels (size_average=True's ssim_map.mean(1)), unclipped — summary.py
+ * clips it to [0, 1] before colouring, which rnerf_errmap_sheet's index does anyway; mean (nullable, not both null): float[n], the mean
+ * of the unclipped per-channel maps, a fixed-order fp64 sum of per-tile partials: the same inputs give the same bits on every run.
+ * `workspace` (rnerf_ssim_summary_workspace_bytes, 8-byte aligned, always needed): the partials, then the per-channel map
+ * float[n][H-fs+1][W-fs+1][C], which a second launch averages over the channels.  The moments are those of rnerf_ssim (same tiles, same
+ * shift before squaring), so sigma is closer to the exact value than ssim.py's float32 blur(x^2) - mu^2.  Argument checks and
+ * RNERF_ERR_UNSUPPORTED as for rnerf_ssim; the workspace query then returns 0. */
+size_t rnerf_ssim_summary_workspace_bytes(int64_t n, int32_t H, int32_t W, int32_t C, int32_t filter_size);
+int rnerf_ssim_summary(const float* img0, const float* img1, int64_t n, int32_t H, int32_t W, int32_t C, int32_t filter_size,
+                       double filter_sigma, double data_range, float* map, float* mean, void* workspace, void* stream);
+
+/* rnerf_errmap_sheet: save_err and the merge of summary.py:40-45,223-240 as finished bytes, one launch.  reference, test: device
+ * float[H][W][3]; maps, map_h, map_w: HOST arrays of K <= 4 device pointers float[map_h[k]][map_w[k]] with 1 <= map_h[k] <= H,
+ * 1 <= map_w[k] <= W; out: device uint8[H][(2 + K)(W + 5)][3].  Columns: reference, 5 of 255, test, 5 of 255, then per map an H x W
+ * panel — the coloured map in its top-left corner, 0 elsewhere — and 5 of 255.  An image value x becomes trunc(clip(255 x, 0, 255))
+ * with the product in double (save_img on the float64 hstack); a map value v becomes the index i = trunc(clip(255 v, 0, 255)) with
+ * the product in float32 (save_err) and then the bytes trunc(255 magma[i]) of csrc/magma_table.h (the PNG round trip of :233 is the
+ * identity on bytes).  NaN, in an image or a map, gives byte or index 0: the reference's cast is undefined there.  The errmap PNGs are
+ * slices of the sheet.  RNERF_ERR_ARG before any device work for null pointers, K outside [0, 4], H or W < 1, a map that is empty or
+ * larger than the image, a sheet of 2^31 bytes or more, an `out` that overlaps an input. */
+int rnerf_errmap_sheet(const float* reference, const float* test, int32_t H, int32_t W, int32_t K, const float* const* maps,
+                       const int32_t* map_h, const int32_t* map_w, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }

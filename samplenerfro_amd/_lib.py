@@ -182,6 +182,12 @@ SIGNATURES = {
     "rnerf_vis_normals": (C.c_int, [_vp, _vp, _i32, _i32, _dbl, _vp, _vp, _vp, _vp]),
     # scene images (csrc/images.hip)
     "rnerf_images_prepare": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    # error maps and the comparison sheet of metric/summary.py (csrc/errmap.hip, csrc/metrics.hip)
+    "rnerf_errmap_mse_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32]),
+    "rnerf_errmap_mse": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "rnerf_ssim_summary_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32, _i32, _i32]),
+    "rnerf_ssim_summary": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp]),
+    "rnerf_errmap_sheet": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -18,6 +18,10 @@
 //
 // The mean is reduced without floating-point atomics: each tile writes one fp64 partial sum; a second launch adds each image's partials
 // in a fixed order.  The same inputs give the same bits on every run.
+//
+// The same tile kernel, instantiated with SUMMARY, is metric/summary.py's SSIM (metric/ssim/ssim.py:45-133, rnerf_ssim_summary): only the
+// formula after the vertical pass differs.  Its per-channel map goes to the workspace and channel_mean_kernel averages the channels.
+// summary.py's squared-error map (rnerf_errmap_mse) is here too, for the fixed-order mean it shares with the other two.
 #include "common.h"
 
 #include <math.h>
@@ -114,7 +118,9 @@ __device__ __forceinline__ void ssim_stage(const float* __restrict__ img0, const
   }
 }
 
-template <int RPT>
+// SUMMARY: metric/ssim/ssim.py:69-81 instead of rnerf/utils.py:455-469 — the same blurred moments, the variances and the covariance neither
+// clamped nor bounded by sign * min, luminance term times contrast-structure term.
+template <int RPT, bool SUMMARY>
 __global__ __launch_bounds__(SSIM_THREADS) void ssim_tile_kernel(const float* __restrict__ img0, const float* __restrict__ img1, int H, int W,
                                                                  int C, int fs, int rc, int lin, int tiles_x, int tiles_y, SsimFilter filt, float c1,
                                                                  float c2, long long total, int vec, float* __restrict__ map,
@@ -214,12 +220,18 @@ __global__ __launch_bounds__(SSIM_THREADS) void ssim_tile_kernel(const float* __
       const float mu0 = m0 + sh0, mu1 = m1 + sh1;
       const float mu00 = mu0 * mu0, mu11 = mu1 * mu1, mu01 = mu0 * mu1;
       float s00 = acc[q][2] - m0 * m0, s11 = acc[q][3] - m1 * m1, s01 = acc[q][4] - m0 * m1;
-      s00 = s00 < 0.f ? 0.f : s00;                      // jnp.maximum(0, s): NaN stays NaN
-      s11 = s11 < 0.f ? 0.f : s11;
-      s01 = nan_sign(s01) * nan_min(sqrtf(s00 * s11), fabsf(s01));
-      const float numer = (2.f * mu01 + c1) * (2.f * s01 + c2);
-      const float denom = (mu00 + mu11 + c1) * (s00 + s11 + c2);
-      const float m = numer / denom;
+      float m;
+      if constexpr (SUMMARY) {
+        const float cs = (2.f * s01 + c2) / (s00 + s11 + c2);
+        m = ((2.f * mu01 + c1) / (mu00 + mu11 + c1)) * cs;
+      } else {
+        s00 = s00 < 0.f ? 0.f : s00;                      // jnp.maximum(0, s): NaN stays NaN
+        s11 = s11 < 0.f ? 0.f : s11;
+        s01 = nan_sign(s01) * nan_min(sqrtf(s00 * s11), fabsf(s01));
+        const float numer = (2.f * mu01 + c1) * (2.f * s01 + c2);
+        const float denom = (mu00 + mu11 + c1) * (s00 + s11 + c2);
+        m = numer / denom;
+      }
       if (map) map[(img * Ho + oy0 + i) * (long long)wo_flat + ox0 + lane] = m;
       part += (double)m;
     }
@@ -245,6 +257,16 @@ __global__ __launch_bounds__(SSIM_THREADS) void ssim_mean_kernel(const double* _
   if (tid == 0) mean[img] = (float)((((red[0] + red[1]) + red[2]) + red[3]) / count);
 }
 
+// The channel mean of a per-channel map float[rows][C] -> float[rows] (ssim_map.mean(1), ssim.py:129): the channels added in order in
+// float32, divided by C.  One thread per pixel.
+__global__ __launch_bounds__(SSIM_THREADS) void channel_mean_kernel(const float* __restrict__ per_channel, long long pixels, int C, float* __restrict__ map) {
+  const long long px = (long long)blockIdx.x * SSIM_THREADS + threadIdx.x;
+  if (px >= pixels) return;
+  float s = per_channel[px * C];
+  for (int c = 1; c < C; ++c) s += per_channel[px * C + c];
+  map[px] = s / (float)C;
+}
+
 int ssim_check(int64_t n, int32_t H, int32_t W, int32_t C, int32_t fs, SsimPlan* p) {
   RNERF_CHECK_ARG(fs >= 1 && fs <= SSIM_MAX_FS, "rnerf_ssim: filter_size must be in [1, %d], got %d", SSIM_MAX_FS, fs);
   RNERF_CHECK_ARG(n >= 1 && C >= 1, "rnerf_ssim: need n >= 1 and C >= 1");
@@ -257,6 +279,54 @@ int ssim_check(int64_t n, int32_t H, int32_t W, int32_t C, int32_t fs, SsimPlan*
   RNERF_CHECK_ARG((long long)p->tiles_x * p->tiles_y * n <= 0xffffffffLL / SSIM_THREADS, "rnerf_ssim: too many tiles for one launch");
   return RNERF_OK;
 }
+
+// ---- The squared-error map of metric/summary.py:49-54 (rnerf_errmap_mse) -------------------------------------------------------------
+//
+// One thread per pixel: map = mean over the channels of (ref - test)^2, each operation one rounded float32 operation, the channels
+// added in order (torch.mean(..., axis=0) over a few channels).  A workgroup covers 256 consecutive pixels of ONE image; its partial is
+// the fp64 sum of the float32 squares.
+__global__ __launch_bounds__(SSIM_THREADS) void errmap_mse_kernel(const float* __restrict__ ref, const float* __restrict__ test, long long hw,
+                                                                    int C, int blocks_per_image, float* __restrict__ map,
+                                                                    double* __restrict__ partials) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x;
+  const long long blk = blockIdx.x;
+  const long long img = blk / blocks_per_image;
+  const long long px = (blk - img * blocks_per_image) * SSIM_THREADS + tid;
+  double part = 0.0;
+  if (px < hw) {
+    const long long at = (img * hw + px) * C;
+    float sum = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float d = fsub(ref[at + c], test[at + c]);
+      const float sq = fmul(d, d);
+      sum = c == 0 ? sq : fadd(sum, sq);
+      part += (double)sq;
+    }
+    if (map) map[img * hw + px] = fdiv(sum, (float)C);
+  }
+  if (partials) {
+    part = wave_sum(part);
+    if ((tid & 63) == 0) red[tid >> 6] = part;
+    __syncthreads();
+    if (tid == 0) partials[blk] = ((red[0] + red[1]) + red[2]) + red[3];
+  }
+}
+
+inline bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+int errmap_mse_check(int64_t n, int32_t H, int32_t W, int32_t C, long long* blocks_per_image) {
+  RNERF_CHECK_ARG(n >= 1 && H >= 1 && W >= 1 && C >= 1, "rnerf_errmap_mse: need n >= 1, H >= 1, W >= 1 and C >= 1");
+  const long long hw = (long long)H * W;
+  *blocks_per_image = (hw + SSIM_THREADS - 1) / SSIM_THREADS;
+  RNERF_CHECK_ARG(*blocks_per_image <= 0x7fffffffLL / n, "rnerf_errmap_mse: n * H * W too large for one launch");
+  RNERF_CHECK_ARG(C <= (1LL << 40) / hw / n, "rnerf_errmap_mse: n * H * W * C too large");
+  return RNERF_OK;
+}
+
 
 // ---- LDR-FLIP (metric/flip/flip_api.py:439-495, compute_ldrflip) ------------------------------------------------------------------
 //
@@ -607,7 +677,7 @@ extern "C" int rnerf_ssim(const float* img0, const float* img1, int64_t n, int32
   double* partials = mean ? (double*)workspace : nullptr;
   const dim3 grid((unsigned)(tiles * n)), block(SSIM_THREADS);
 #define RNERF_SSIM_LAUNCH(R)                                                                                                              \
-  hipLaunchKernelGGL(ssim_tile_kernel<R>, grid, block, p.lds, st, img0, img1, H, W, C, fs, p.rc, p.lin, p.tiles_x, p.tiles_y, filt, c1, c2, \
+  hipLaunchKernelGGL((ssim_tile_kernel<R, false>), grid, block, p.lds, st, img0, img1, H, W, C, fs, p.rc, p.lin, p.tiles_x, p.tiles_y, filt, c1, c2, \
                      total, vec, map, partials)
   switch (p.rpt) {
     case 4: RNERF_SSIM_LAUNCH(4); break;
@@ -619,6 +689,96 @@ extern "C" int rnerf_ssim(const float* img0, const float* img1, int64_t n, int32
   if (mean) {
     const double count = (double)(H - fs + 1) * (double)(W - fs + 1) * (double)C;
     hipLaunchKernelGGL(ssim_mean_kernel, dim3((unsigned)n), dim3(SSIM_THREADS), 0, st, partials, (int)tiles, count, mean);
+    RNERF_CHECK_LAUNCH();
+  }
+  return RNERF_OK;
+}
+
+extern "C" size_t rnerf_errmap_mse_workspace_bytes(int64_t n, int32_t H, int32_t W) {
+  long long bpi;
+  if (errmap_mse_check(n, H, W, 1, &bpi) != RNERF_OK) return 0;
+  return (size_t)n * (size_t)bpi * sizeof(double);
+}
+
+extern "C" int rnerf_errmap_mse(const float* reference, const float* test, int64_t n, int32_t H, int32_t W, int32_t C, float* map, float* mean,
+                                void* workspace, void* stream) {
+  long long bpi;
+  const int rc = errmap_mse_check(n, H, W, C, &bpi);
+  if (rc != RNERF_OK) return rc;
+  RNERF_CHECK_ARG(reference && test && (map || mean), "rnerf_errmap_mse: null pointer (reference, test, and map or mean)");
+  RNERF_CHECK_ARG(!mean || workspace, "rnerf_errmap_mse: the mean needs the workspace (rnerf_errmap_mse_workspace_bytes)");
+  RNERF_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "rnerf_errmap_mse: the workspace must be 8-byte aligned");
+  const long long hw = (long long)H * W;
+  const size_t in_bytes = (size_t)n * hw * C * sizeof(float);
+  if (map)
+    RNERF_CHECK_ARG(!overlaps(map, (size_t)n * hw * sizeof(float), reference, in_bytes) && !overlaps(map, (size_t)n * hw * sizeof(float), test, in_bytes),
+                    "rnerf_errmap_mse: map overlaps an input");
+  hipStream_t st = (hipStream_t)stream;
+  double* partials = mean ? (double*)workspace : nullptr;
+  hipLaunchKernelGGL(errmap_mse_kernel, dim3((unsigned)(n * bpi)), dim3(SSIM_THREADS), 0, st, reference, test, hw, C, (int)bpi, map, partials);
+  RNERF_CHECK_LAUNCH();
+  if (mean) {
+    hipLaunchKernelGGL(ssim_mean_kernel, dim3((unsigned)n), dim3(SSIM_THREADS), 0, st, partials, (int)bpi, (double)hw * (double)C, mean);
+    RNERF_CHECK_LAUNCH();
+  }
+  return RNERF_OK;
+}
+
+// workspace of rnerf_ssim_summary: one fp64 partial per tile, then the per-channel map float[n][H-fs+1][W-fs+1][C]
+inline size_t ssim_summary_partials_bytes(int64_t n, const SsimPlan& p) { return (size_t)n * p.tiles_x * p.tiles_y * sizeof(double); }
+
+extern "C" size_t rnerf_ssim_summary_workspace_bytes(int64_t n, int32_t H, int32_t W, int32_t C, int32_t filter_size) {
+  SsimPlan p;
+  if (ssim_check(n, H, W, C, filter_size, &p) != RNERF_OK) return 0;
+  return ssim_summary_partials_bytes(n, p) + (size_t)n * (H - filter_size + 1) * (W - filter_size + 1) * C * sizeof(float);
+}
+
+extern "C" int rnerf_ssim_summary(const float* img0, const float* img1, int64_t n, int32_t H, int32_t W, int32_t C, int32_t filter_size,
+                                  double filter_sigma, double data_range, float* map, float* mean, void* workspace, void* stream) {
+  SsimPlan p;
+  const int rc = ssim_check(n, H, W, C, filter_size, &p);
+  if (rc != RNERF_OK) return rc;
+  RNERF_CHECK_ARG(filter_sigma > 0.0 && isfinite(filter_sigma), "rnerf_ssim_summary: filter_sigma must be finite and > 0");
+  RNERF_CHECK_ARG(isfinite(data_range), "rnerf_ssim_summary: data_range must be finite");
+  RNERF_CHECK_ARG(img0 && img1 && (map || mean), "rnerf_ssim_summary: null pointer (img0, img1, and map or mean)");
+  RNERF_CHECK_ARG(workspace, "rnerf_ssim_summary: the per-channel map and the mean need the workspace (rnerf_ssim_summary_workspace_bytes)");
+  RNERF_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "rnerf_ssim_summary: the workspace must be 8-byte aligned");
+  // _fspecial_gauss_1d (ssim.py:20-24), in double, rounded once
+  const int fs = filter_size;
+  double w[SSIM_MAX_FS], sum = 0.0;
+  for (int i = 0; i < fs; ++i) {
+    const double t = (double)(i - fs / 2);
+    w[i] = exp(-(t * t) / (2.0 * filter_sigma * filter_sigma));
+    sum += w[i];
+  }
+  RNERF_CHECK_ARG(sum > 0.0 && isfinite(sum), "rnerf_ssim_summary: the filter's weights sum to %g", sum);
+  SsimFilter filt = {};
+  for (int i = 0; i < fs; ++i) filt.w[i] = (float)(w[i] / sum);
+  const float c1 = (float)((0.01 * data_range) * (0.01 * data_range)), c2 = (float)((0.03 * data_range) * (0.03 * data_range));
+  const long long total = n * H * (long long)W * C;
+  const int vec = ((((uintptr_t)img0) | ((uintptr_t)img1)) & 15) == 0;
+  const long long tiles = (long long)p.tiles_x * p.tiles_y;
+  hipStream_t st = (hipStream_t)stream;
+  double* partials = mean ? (double*)workspace : nullptr;
+  float* per_channel = map ? (float*)((char*)workspace + ssim_summary_partials_bytes(n, p)) : nullptr;
+  const dim3 grid((unsigned)(tiles * n)), block(SSIM_THREADS);
+#define RNERF_SSIM_LAUNCH(R)                                                                                                                    \
+  hipLaunchKernelGGL((ssim_tile_kernel<R, true>), grid, block, p.lds, st, img0, img1, H, W, C, fs, p.rc, p.lin, p.tiles_x, p.tiles_y, filt, c1, \
+                     c2, total, vec, per_channel, partials)
+  switch (p.rpt) {
+    case 4: RNERF_SSIM_LAUNCH(4); break;
+    case 2: RNERF_SSIM_LAUNCH(2); break;
+    default: RNERF_SSIM_LAUNCH(1); break;
+  }
+#undef RNERF_SSIM_LAUNCH
+  RNERF_CHECK_LAUNCH();
+  const long long pixels = n * (long long)(H - fs + 1) * (W - fs + 1);
+  if (map) {
+    hipLaunchKernelGGL(channel_mean_kernel, dim3((unsigned)((pixels + SSIM_THREADS - 1) / SSIM_THREADS)), dim3(SSIM_THREADS), 0, st, per_channel, pixels, C, map);
+    RNERF_CHECK_LAUNCH();
+  }
+  if (mean) {
+    hipLaunchKernelGGL(ssim_mean_kernel, dim3((unsigned)n), dim3(SSIM_THREADS), 0, st, partials, (int)tiles, (double)pixels / (double)n * (double)C, mean);
     RNERF_CHECK_LAUNCH();
   }
   return RNERF_OK;

@@ -7,6 +7,8 @@ each view is also scored with LDR-FLIP (utils.compute_flip, rnerf_flip; metric/s
 With masks / mask_mode the views are scored on the object's region and / or the crop around it (summary.py:91-92,177-205,
 metric/compare.py:132-133,167-197; the masks come from mesh_mask.render_masks).  With vis_suite the depth visualisations of
 eval.py:175,196-198 (vis.visualize_suite: rnerf_vis_depth, rnerf_vis_normals) are computed for every view and written with save_output.
+With errmap=True every view also gets metric/summary.py's error maps, comparison sheet and numbers (errmap.error_maps, errmap.sheet:
+rnerf_errmap_mse, rnerf_ssim_summary, rnerf_flip, rnerf_errmap_sheet), scored on the 8-bit prediction as summary.py scores the PNG.
 """
 from __future__ import annotations
 
@@ -92,7 +94,8 @@ def apply_mask(pred_color: torch.Tensor, pixels: torch.Tensor, mask, mask_mode: 
 
 def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192, normalize_disp: bool = False, out_dir: Optional[str] = None,
              step=None, save_output: bool = False, render_path: bool = False, flip: bool = False,
-             flip_pixels_per_degree: Optional[float] = None, masks=None, mask_mode: Optional[str] = None, vis_suite: bool = False) -> dict:
+             flip_pixels_per_degree: Optional[float] = None, masks=None, mask_mode: Optional[str] = None, vis_suite: bool = False,
+             errmap: bool = False) -> dict:
     """Render and score every view (eval.py:155-215).
 
     model / variables: what models.construct_nerf returns; views: batches as device_views yields them; rng: the render key (eval.py passes
@@ -117,7 +120,20 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
 
     vis_suite=True computes vis.visualize_suite(pred_disp[..., 0], pred_acc[..., 0]) for every view (eval.py:175; seven more launches, no
     read-back); with save_output it also writes depth_{idx:03d}.png, depth_mod_{idx:03d}.png and depth_normals_{idx:03d}.png
-    (eval.py:196-198) through utils.save_img.  With vis_suite=False the keys, the files and the launches are those of the loop without it."""
+    (eval.py:196-198) through utils.save_img.  With vis_suite=False the keys, the files and the launches are those of the loop without it.
+
+    errmap=True: metric/summary.py for every view with ground truth — errmap.error_maps(pixels, errmap.quantize8(pred_color)) (summary.py
+    scores the PNG it reads back, not the float render; masked and / or cropped first with masks / mask_mode, :197-205, so a cropped view
+    gives a cropped sheet) and one errmap.sheet.  The result gains "summary": {"psnrs", "ssims", "flips", "psnr", "ssim", "flip"}
+    (summary.py's PSNR of the quantised image, the pytorch-msssim SSIM, FLIP at utils.FLIP_PPD_SUMMARY); the three floats ride in the
+    view's one read-back.  With save_output the sheet is read back (one uint8 image per view) and errmap.write_error_maps writes
+    errmap{suffix}/psnr_{idx:03d}.png, ssim_..., flip_... and errmap{suffix}/frame{suffix}/frame_{idx:03d}.png; after the loop
+    metric_list{suffix}.txt and result{suffix}.txt (summary.py:243-250 without the LPIPS column).  Not with render_path (ValueError).
+    With errmap=False the keys, the files and the launches are those of the loop without it."""
+    if errmap and render_path:
+        raise ValueError("evaluate: errmap needs ground truth, render_path has none")
+    if errmap:
+        from . import errmap as em
     if (masks is None) != (mask_mode is None):
         raise ValueError("evaluate: masks and mask_mode go together (got only one of them)")
     suffix = mask_suffix(mask_mode)
@@ -131,6 +147,7 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
         return model.apply(variables, key_0, key_1, rays, False, path=path)
 
     psnr_values, ssim_values, flip_values = [], [], []
+    summary_values = ([], [], [])
     num_rays = 0
     t0 = time.perf_counter()
     for idx, batch in enumerate(views):
@@ -138,22 +155,37 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
         num_rays += int(pred_color.shape[0]) * int(pred_color.shape[1])
         if not render_path:
             scored, pixels = pred_color, batch["pixels"]
+            if errmap:
+                scored8 = em.quantize8(scored)
+                if mask_iter is not None:
+                    scored = torch.cat([scored, scored8], dim=-1)             # masked and cropped together with the float render
             if mask_iter is not None:
                 try:
                     mask = next(mask_iter)
                 except StopIteration:
                     raise ValueError(f"evaluate: masks ran out at view {idx}") from None
                 scored, pixels = apply_mask(scored, pixels, mask, mask_mode)
+                if errmap:
+                    scored, scored8 = scored[..., :3].contiguous(), scored[..., 3:].contiguous()
             psnr = utils.compute_psnr(((scored - pixels) ** 2).mean())
             ssim = utils.compute_ssim(scored, pixels, max_val=1.0)
             scores = [psnr.to(torch.float32), ssim]
             if flip:
                 scores.append(utils.compute_flip(scored, pixels, flip_pixels_per_degree))
+            if errmap:
+                maps = em.error_maps(pixels, scored8)
+                sheet = em.sheet(pixels, scored8, [maps[name] for name in em.MAP_NAMES])
+                scores += [maps[name + "_value"] for name in em.MAP_NAMES]
             pair = torch.stack(scores).cpu()                                  # the one read-back of the view: 8 bytes (12 with flip)
             psnr_values.append(float(pair[0]))
             ssim_values.append(float(pair[1]))
             if flip:
                 flip_values.append(float(pair[2]))
+            if errmap:
+                for values, v in zip(summary_values, pair[-3:]):
+                    values.append(float(v))
+                if save_output:
+                    em.write_error_maps(out_dir, idx, sheet, [tuple(maps[name].shape) for name in em.MAP_NAMES], suffix)
         if save_output:
             utils.save_img(pred_color, os.path.join(out_dir, "{:03d}.png".format(idx)))
             utils.save_img(pred_disp[..., 0], os.path.join(out_dir, "disp_{:03d}.png".format(idx)))
@@ -168,6 +200,8 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
     seconds = time.perf_counter() - t0
     if save_output and not render_path:
         write_metric_files(out_dir, step, psnr_values, ssim_values, flip_values if flip else None, suffix)
+        if errmap and summary_values[0]:
+            em.write_summary_files(out_dir, *summary_values, suffix)
     have = bool(psnr_values)
     res = {"psnrs": psnr_values, "ssims": ssim_values,
            "psnr": float(np.mean(np.array(psnr_values))) if have else None,
@@ -178,4 +212,8 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
         res["flip"] = float(np.mean(np.array(flip_values))) if flip_values else None
     if mask_mode is not None:
         res["mask_mode"] = mask_mode
+    if errmap:
+        mean = lambda v: float(np.mean(np.array(v))) if v else None
+        res["summary"] = {"psnrs": summary_values[0], "ssims": summary_values[1], "flips": summary_values[2],
+                          "psnr": mean(summary_values[0]), "ssim": mean(summary_values[1]), "flip": mean(summary_values[2])}
     return res

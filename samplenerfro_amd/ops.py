@@ -664,11 +664,11 @@ def ssim(img0: torch.Tensor, img1: torch.Tensor, *, max_val: float, filter_size:
 _flip_workspaces: dict = {}       # (device index, stream) -> uint8 tensor: rnerf_flip's workspace, kept and grown between calls
 
 
-def flip(reference: torch.Tensor, test: torch.Tensor, *, pixels_per_degree: float, return_map: bool = False) -> torch.Tensor:
+def flip(reference: torch.Tensor, test: torch.Tensor, *, pixels_per_degree: float, return_map: bool = False, return_both: bool = False):
     """compute_ldrflip (metric/flip/flip_api.py:439-495) on the device (rnerf_flip).  reference, test: float32 device tensors
     [..., H, W, 3], sRGB in [0, 1].  -> the mean FLIP error of each image, shape [...] (0-dim for [H, W, 3]), or with return_map the
     error map [..., H, W].  Issued on the current stream of the images' device; nothing is synchronised.  The workspace (14 filtered
-    planes) is kept per device and stream and reused by later calls that fit in it."""
+    planes) is kept per device and stream and reused by later calls that fit in it.  return_both: -> (map, mean) from the one call."""
     if tuple(reference.shape) != tuple(test.shape):
         raise ValueError(f"flip: the images differ in shape: {tuple(reference.shape)} vs {tuple(test.shape)}")
     if reference.dim() < 3 or int(reference.shape[-1]) != 3:
@@ -683,7 +683,8 @@ def flip(reference: torch.Tensor, test: torch.Tensor, *, pixels_per_degree: floa
         n *= s
     dev = a.device
     if n == 0 or H == 0 or W == 0:
-        return torch.empty(tuple(lead) + ((H, W) if return_map else ()), dtype=torch.float32, device=dev)
+        empty = lambda shape: torch.empty(tuple(lead) + shape, dtype=torch.float32, device=dev)
+        return (empty((H, W)), empty(())) if return_both else empty((H, W) if return_map else ())
     lib = _lib.load()
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -694,10 +695,109 @@ def flip(reference: torch.Tensor, test: torch.Tensor, *, pixels_per_degree: floa
         ws = _flip_workspaces.get(key)
         if ws is None or ws.numel() < nb:
             ws = _flip_workspaces[key] = torch.empty(nb, dtype=torch.uint8, device=dev)
-        out_map = torch.empty(tuple(lead) + (H, W), dtype=torch.float32, device=dev) if return_map else None
-        mean = None if return_map else torch.empty(tuple(lead), dtype=torch.float32, device=dev)
+        out_map = torch.empty(tuple(lead) + (H, W), dtype=torch.float32, device=dev) if return_map or return_both else None
+        mean = None if return_map and not return_both else torch.empty(tuple(lead), dtype=torch.float32, device=dev)
         check(lib.rnerf_flip(ptr(a), ptr(b), n, H, W, ppd, ptr(out_map), ptr(mean), ptr(ws), stream), "rnerf_flip")
+    if return_both:
+        return out_map, mean
     return out_map if return_map else mean
+
+
+def _image_pair(a: torch.Tensor, b: torch.Tensor, what: str):
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"{what}: the images differ in shape: {tuple(a.shape)} vs {tuple(b.shape)}")
+    if a.dim() < 3:
+        raise ValueError(f"{what}: need [..., H, W, C] images, got shape {tuple(a.shape)}")
+    if a.device != b.device:
+        raise ValueError(f"{what}: the images are on different devices ({a.device}, {b.device})")
+    *lead, H, W, Ch = (int(s) for s in a.shape)
+    n = 1
+    for s in lead:
+        n *= s
+    return _chk(a, "reference"), _chk(b, "test"), tuple(lead), n, H, W, Ch
+
+
+def errmap_mse(reference: torch.Tensor, test: torch.Tensor, *, want_map: bool = True, want_mean: bool = True):
+    """compute_psnr's map and mean squared error (metric/summary.py:49-54) on the device (rnerf_errmap_mse).  reference, test: float32
+    device tensors [..., H, W, C].  -> (map [..., H, W], the mean over the channels of the squared difference; mean [...], each image's
+    MSE), None for what was not wanted.  Issued on the current stream of the images' device; nothing is synchronised."""
+    a, b, lead, n, H, W, Ch = _image_pair(reference, test, "errmap_mse")
+    if not (want_map or want_mean):
+        raise ValueError("errmap_mse: nothing wanted")
+    if n == 0 or H == 0 or W == 0 or Ch == 0:
+        raise ValueError(f"errmap_mse: empty images, shape {tuple(reference.shape)}")
+    lib = _lib.load()
+    dev = a.device
+    with torch.cuda.device(dev):
+        out_map = torch.empty(lead + (H, W), dtype=torch.float32, device=dev) if want_map else None
+        mean, ws = None, None
+        if want_mean:
+            mean = torch.empty(lead, dtype=torch.float32, device=dev)
+            nb = lib.rnerf_errmap_mse_workspace_bytes(n, H, W)
+            if nb == 0:
+                check(-1, "rnerf_errmap_mse_workspace_bytes")
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        check(lib.rnerf_errmap_mse(ptr(a), ptr(b), n, H, W, Ch, ptr(out_map), ptr(mean), ptr(ws), torch.cuda.current_stream(dev).cuda_stream),
+              "rnerf_errmap_mse")
+    return out_map, mean
+
+
+def ssim_summary(img0: torch.Tensor, img1: torch.Tensor, *, data_range: float = 1.0, filter_size: int = 11, filter_sigma: float = 1.5,
+                 want_map: bool = True, want_mean: bool = True):
+    """metric/ssim/ssim.py:45-133 as metric/summary.py:56-61,115 calls it, on the device (rnerf_ssim_summary): the pytorch-msssim
+    formula, not ops.ssim's.  img0, img1: float32 device tensors [..., H, W, C].  -> (map [..., H-fs+1, W-fs+1], the channel mean,
+    unclipped; mean [...], the mean of the per-channel maps), None for what was not wanted.  Nothing is synchronised."""
+    a, b, lead, n, H, W, Ch = _image_pair(img0, img1, "ssim_summary")
+    fs = int(filter_size)
+    if not (want_map or want_mean):
+        raise ValueError("ssim_summary: nothing wanted")
+    if not 1 <= fs <= 31:
+        raise ValueError(f"ssim_summary: filter_size must be in [1, 31], got {fs}")
+    if H < fs or W < fs:
+        raise ValueError(f"ssim_summary: the images ({H} x {W}) are smaller than the window (filter_size {fs})")
+    if n == 0 or Ch == 0:
+        raise ValueError(f"ssim_summary: empty images, shape {tuple(img0.shape)}")
+    lib = _lib.load()
+    dev = a.device
+    with torch.cuda.device(dev):
+        nb = lib.rnerf_ssim_summary_workspace_bytes(n, H, W, Ch, fs)
+        if nb == 0:
+            check(-1, "rnerf_ssim_summary_workspace_bytes")
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        out_map = torch.empty(lead + (H - fs + 1, W - fs + 1), dtype=torch.float32, device=dev) if want_map else None
+        mean = torch.empty(lead, dtype=torch.float32, device=dev) if want_mean else None
+        check(lib.rnerf_ssim_summary(ptr(a), ptr(b), n, H, W, Ch, fs, float(filter_sigma), float(data_range), ptr(out_map), ptr(mean), ptr(ws),
+                                     torch.cuda.current_stream(dev).cuda_stream), "rnerf_ssim_summary")
+    return out_map, mean
+
+
+def errmap_sheet(reference: torch.Tensor, test: torch.Tensor, maps) -> torch.Tensor:
+    """The comparison sheet of metric/summary.py:231-240 as bytes (rnerf_errmap_sheet).  reference, test: float32 device tensors
+    [H, W, 3]; maps: up to four float32 device tensors [h_k, w_k] with h_k <= H, w_k <= W.  -> uint8 [H, (2 + K)(W + 5), 3]: reference |
+    test | each map through the magma bytes in the top-left corner of a black H x W panel, 5 columns of 255 after every panel.  One
+    launch on the current stream of the images' device; nothing is synchronised."""
+    if tuple(reference.shape) != tuple(test.shape) or reference.dim() != 3 or int(reference.shape[2]) != 3:
+        raise ValueError(f"errmap_sheet: need two [H, W, 3] images, got {tuple(reference.shape)} and {tuple(test.shape)}")
+    a, b = _chk(reference, "reference"), _chk(test, "test")
+    H, W = int(a.shape[0]), int(a.shape[1])
+    dev = a.device
+    ms = []
+    for k, m in enumerate(maps):
+        if m.dim() != 2 or m.device != dev:
+            raise ValueError(f"errmap_sheet: map {k} must be a [h, w] tensor on {dev}, got {tuple(m.shape)} on {m.device}")
+        ms.append(_chk(m, f"map {k}"))
+    K = len(ms)
+    if b.device != dev or H < 1 or W < 1:
+        raise ValueError(f"errmap_sheet: the images must be non-empty and on one device, got {tuple(a.shape)} on {a.device} and {b.device}")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        out = torch.empty((H, (2 + K) * (W + 5), 3), dtype=torch.uint8, device=dev)
+        ptrs = (C.c_void_p * max(K, 1))(*[m.data_ptr() for m in ms])
+        hs = (C.c_int32 * max(K, 1))(*[int(m.shape[0]) for m in ms])
+        wds = (C.c_int32 * max(K, 1))(*[int(m.shape[1]) for m in ms])
+        check(lib.rnerf_errmap_sheet(ptr(a), ptr(b), H, W, K, ptrs, hs, wds, ptr(out), torch.cuda.current_stream(dev).cuda_stream),
+              "rnerf_errmap_sheet")
+    return out
 
 
 def _vis_plane(t, name: str) -> torch.Tensor:
