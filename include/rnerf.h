@@ -252,8 +252,8 @@ int rnerf_so3_query(const float* table, const rnerf_grid* g, const float* so3_pa
  * dims[0] * dims[1] * dims[2] * 16 B < 4 GiB in all of them; rnerf_march_all / rnerf_march_all_train / rnerf_march_adjoint (and
  * rnerf_march on a BRICKS table) need the stride of TWO x-planes below 2^24: dims[1] * dims[2] * 32 < 2^24 (reference order;
  * ceil(dims[1]/2) * ceil(dims[2]/2) * 128 < 2^24 for bricks); rnerf_march on a REFERENCE-order table needs only dims[1] * dims[2] * 16 < 2^24.
- * Cubic grids up to 645^3 pass every check (every shipped config: 128^3 .. 512^3); larger grids are rejected with RNERF_ERR_ARG, never
- * mis-addressed. */
+ * Cubic grids up to 645^3 in reference order and 644^3 in bricks (odd dimensions are padded to whole bricks) pass every check (every
+ * shipped config: 128^3 .. 512^3); larger grids are rejected with RNERF_ERR_ARG ("grid too large"), never mis-addressed. */
 size_t rnerf_so3_packed_bytes(void);
 int rnerf_march_all(const float* table, const rnerf_grid* g, const float* so3_params, void* so3_packed, const float* window10, const float* origins,
                     const float* viewdirs, int32_t B, double near, double far, int32_t num_nodes, float* path_pd, float* path_dr,

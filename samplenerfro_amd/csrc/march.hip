@@ -193,7 +193,7 @@ extern "C" int rnerf_march(const float* table, const rnerf_grid* g, const float*
                   "rnerf_march: table/path buffers must be 16-byte aligned");
   GridParams gp;
   RNERF_CHECK_ARG(make_grid_params(g, &gp), "rnerf_march: bad grid");
-  RNERF_CHECK_ARG(grid_fits_march(gp), "rnerf_march: grid too large for 32-bit byte offsets (needs a table < 4 GiB and 24-bit row strides)");
+  RNERF_CHECK_ARG(grid_fits_march(gp), "rnerf_march: grid too large for 32-bit byte offsets (needs a table < 4 GiB and 24-bit strides: the row strides in reference order, the brick strides in bricks)");
   MarchParams p;
   p.dx = gp.dx; p.dy = gp.dy; p.dz = gp.dz;
   p.nmin[0] = gp.nminx; p.nmin[1] = gp.nminy; p.nmin[2] = gp.nminz;

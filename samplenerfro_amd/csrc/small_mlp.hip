@@ -1148,7 +1148,7 @@ extern "C" int rnerf_march_all(const float* table, const rnerf_grid* g, const fl
   RNERF_CHECK_ARG(make_grid_params(g, &gp), "rnerf_march_all: bad grid");
   So3Window w;
   for (int i = 0; i < 10; ++i) w.w[i] = window10[i];
-  RNERF_CHECK_ARG(grid_fits_u32(gp), "rnerf_march_all: grid too large for 32-bit byte offsets (needs a table < 4 GiB)");
+  RNERF_CHECK_ARG(grid_fits_u32(gp), "rnerf_march_all: grid too large for 32-bit byte offsets (needs a table < 4 GiB and 24-bit strides of index >> 1: twice the row strides in reference order, the brick strides in bricks)");
   const float stepf = (float)((far - near) / (num_nodes - 1));  // models.py:122
   hipLaunchKernelGGL(so3_pack16_kernel, dim3((kSo3Blocks * 64 + 255) / 256), dim3(256), 0, (hipStream_t)stream, so3_params, (uint4*)so3_packed);
   hipLaunchKernelGGL(march_all_kernel, dim3((unsigned)((B + 15) / 16)), dim3(256), 0, (hipStream_t)stream, (const float4*)table, gp, so3_params,
@@ -1169,7 +1169,7 @@ extern "C" int rnerf_march_all_train(const float* table, const rnerf_grid* g, co
   RNERF_CHECK_ARG(make_grid_params(g, &gp), "rnerf_march_all_train: bad grid");
   So3Window w;
   for (int i = 0; i < 10; ++i) w.w[i] = window10[i];
-  RNERF_CHECK_ARG(grid_fits_u32(gp), "rnerf_march_all_train: grid too large for 32-bit byte offsets (needs a table < 4 GiB)");
+  RNERF_CHECK_ARG(grid_fits_u32(gp), "rnerf_march_all_train: grid too large for 32-bit byte offsets (needs a table < 4 GiB and 24-bit strides of index >> 1: twice the row strides in reference order, the brick strides in bricks)");
   const float stepf = (float)((far - near) / (num_nodes - 1));
   hipStream_t st = (hipStream_t)stream;
   RNERF_CHECK_HIP(hipMemsetAsync(pair_count, 0, sizeof(int32_t), st));
@@ -1225,7 +1225,7 @@ extern "C" int rnerf_march_adjoint(const float* table, const rnerf_grid* g, cons
   RNERF_CHECK_ARG(B > 0 && num_nodes >= 2, "rnerf_march_adjoint: need B > 0 and num_nodes >= 2");
   GridParams gp;
   RNERF_CHECK_ARG(make_grid_params(g, &gp), "rnerf_march_adjoint: bad grid");
-  RNERF_CHECK_ARG(grid_fits_u32(gp), "rnerf_march_adjoint: grid too large for 32-bit byte offsets (needs a table < 4 GiB)");
+  RNERF_CHECK_ARG(grid_fits_u32(gp), "rnerf_march_adjoint: grid too large for 32-bit byte offsets (needs a table < 4 GiB and 24-bit strides of index >> 1: twice the row strides in reference order, the brick strides in bricks)");
   const float stepf = (float)((far - near) / (num_nodes - 1));
   hipLaunchKernelGGL(march_adjoint_kernel, dim3((unsigned)((B + 15) / 16)), dim3(64), 0, (hipStream_t)stream, (const float4*)table, gp,
                      (const float4*)path_pd, (const float4*)path_rdn, (const int*)pair_of_node, A12, P12, (const float4*)a_pos, (const float4*)a_dir,

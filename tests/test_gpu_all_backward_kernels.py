@@ -26,6 +26,8 @@ torch = pytest.importorskip("torch")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 import all_backward_ref as AR          # noqa: E402
+from all_backward_dev import D, T, check_scan, jacobian_cotangents, pad4, rel, twice          # noqa: E402
+import all_backward_dev as AD          # noqa: E402
 from oracle import ref_np as R, torch_ref as TR          # noqa: E402
 from samplenerfro_amd import _lib          # noqa: E402
 
@@ -35,30 +37,6 @@ NDIM, NMIN, NMAX = [20, 24, 28], [-1.4, -1.5, -1.6], [1.5, 1.6, 1.4]
 LAYOUTS = ("reference", "bricks")
 SO3_CEIL, ADJ_CEIL = 2e-5, 5e-5
 RELU_MARGIN = 1e-5
-
-
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def D(t):
-    return t.detach().cpu().double()
-
-
-def pad4(a):
-    return np.concatenate([a, np.zeros(a.shape[:-1] + (1,), a.dtype)], -1)
-
-
-def rel(dev, ref):
-    return float((D(dev) - ref).abs().max()) / float(ref.abs().max())
-
-
-def twice(fn):
-    """Run a kernel twice: identical bits (none of the five has atomics in its sums)."""
-    a, b = fn(), fn()
-    for x, y in zip(a if isinstance(a, tuple) else (a,), b if isinstance(b, tuple) else (b,)):
-        assert torch.equal(x, y), "two runs of the same kernel on the same inputs differ"
-    return a
 
 
 SEMI_AXES = [1.35, 1.45, 1.25]
@@ -92,22 +70,13 @@ def scene():
 
 
 def _cells(p, a, f):
-    """(i0, i1, t) of VoxMLP._linear3 along axis a in the float type f: np.float32 repeats the device's arithmetic (fp32 nmin and spacing,
-    common.h: make_grid_params; IEEE subtract, divide, floor), np.float64 the reference's."""
-    nd = (NMAX[a] - NMIN[a]) / (NDIM[a] - 1.0)
-    x = (p.astype(f) - f(NMIN[a])) / f(nd)
-    i = np.floor(x)
-    return np.clip(i, 0, NDIM[a] - 1), np.clip(i + 1, 0, NDIM[a] - 1), x - i
+    """(i0, i1, t) of VoxMLP._linear3 along axis a of this file's grid in the float type f (all_backward_dev.cells)."""
+    return AD.cells(p, a, f, NDIM, NMIN, NMAX)
 
 
 def same_cells(pts64):
-    """True where the device's fp32 corner indices of a point are the float64 reference's on all three axes: the interpolant's position
-    gradient jumps from cell to cell, so a point within an fp32 rounding of a lattice plane has two legitimate answers."""
-    ok = np.ones(pts64.shape[0], bool)
-    for a in range(3):
-        c32, c64 = _cells(pts64[:, a].numpy(), a, np.float32), _cells(pts64[:, a].numpy(), a, np.float64)
-        ok &= (c32[0] == c64[0]) & (c32[1] == c64[1])
-    return torch.from_numpy(ok)
+    """True where the device's fp32 corner indices of a point are the float64 reference's on all three axes (all_backward_dev.same_cells)."""
+    return AD.same_cells(pts64, NDIM, NMIN, NMAX)
 
 
 def lattice_point(a, k):
@@ -150,9 +119,7 @@ def so3_case(alpha):
     pts4, cot4 = T(pad4(pts)), T(pad4(cot))
     raw, save = so3_forward_twice(sc["so3_d"], w, pts4)
     dx = twice(lambda: ops.so3_backward(sc["so3_d"], w, pts4, save, cot4))
-    eye = torch.zeros((3 * n, 4), dtype=torch.float32, device="cuda:0")      # exactly as train._all_stage_backward builds it
-    for j in range(3):
-        eye[j * n:(j + 1) * n, j] = 1.0
+    eye = jacobian_cotangents(n)      # exactly as train._all_stage_backward builds it
     J = twice(lambda: ops.so3_backward(sc["so3_d"], w, pts4, save, eye))
     return dict(n=n, w=w, pts4=pts4, cot4=cot4, raw=raw, save=save, dx=dx, J=J, ref=ref, ref32=ref32, x64=x64)
 
@@ -294,9 +261,7 @@ def adjoint_case():
     n = rec["n_pairs"]
     assert n > 100
     raw, save = ops.so3_forward_train(sc["so3_d"], rec["window"], rec["pair_x"])
-    eye = torch.zeros((3 * n, 4), dtype=torch.float32, device="cuda:0")
-    for j in range(3):
-        eye[j * n:(j + 1) * n, j] = 1.0
+    eye = jacobian_cotangents(n)
     J = ops.so3_backward(sc["so3_d"], rec["window"], rec["pair_x"], save, eye)
     A, P = ops.so3_pair_jacobian(tab, spec, rec["pair_x"], rec["pair_g"], raw.contiguous(), J)
     rng = np.random.default_rng(41)
@@ -347,20 +312,7 @@ def _scan(c, n_last, synthetic, pairs=True):
 
 
 def _check_scan(tag, v, ref, ref32, inside):
-    vd = D(v)
-    nv = vd.shape[0]
-    assert float(ref[nv:].abs().max() if ref.shape[0] > nv else 0.0) == 0.0
-    m, ref, ref32 = inside[:nv], ref[:nv], ref32[:nv]
-    assert float(vd[~m].abs().max() if bool((~m).any()) else 0.0) == 0.0, "a pair outside the scanned nodes was written"
-    assert float(vd[:, 3].abs().max()) == 0.0
-    if not bool(m.any()) or float(ref.abs().max()) == 0.0:
-        assert float(vd.abs().max()) == 0.0 and float(ref.abs().max()) == 0.0
-        print(f"march_adjoint {tag}: no pair with a cotangent among these nodes, v is exactly zero")
-        return
-    floor, tol = AR.floor_and_tol(ref, ref32, ADJ_CEIL)
-    err = rel(vd[:, :3], ref)
-    print(f"march_adjoint {tag}: {int(m.sum())} pairs, v err {err:.2e} (fp32 floor {floor:.2e}, tol {tol:.2e}), max |v| {float(ref.abs().max()):.2e}")
-    assert err < tol
+    check_scan(tag, v, ref, ref32, inside, ADJ_CEIL)
 
 
 @pytest.mark.parametrize("n_last", [2, 3, 11, 12, 13, 23, 24, 32, 36])
