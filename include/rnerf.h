@@ -756,7 +756,7 @@ int rnerf_images_prepare(const uint8_t* src, int64_t n, int32_t H, int32_t W, in
 
 /* ---- error maps and the comparison sheet of metric/summary.py (csrc/metrics.hip, csrc/errmap.hip) --------------------------------------
  * Appended; RNERF_VERSION stays 4.  What summary.py writes per view besides its numbers: errmap/psnr_NNN.png, ssim_NNN.png, flip_NNN.png
- * and errmap/frame/frame_NNN.png.  The FLIP map is rnerf_flip's `map`.  The LPIPS panel and column are not reproduced.
+ * and errmap/frame/frame_NNN.png.  The FLIP map is rnerf_flip's `map`, the LPIPS map (lpips_NNN.png, the third panel) rnerf_lpips' `map`, for a caller who has the weights.
  *
  * rnerf_errmap_mse: compute_psnr's map and mean squared error (summary.py:49-54).  reference, test: float[n][H][W][C]; map (nullable):
  * float[n][H][W], the mean over the channels of (reference - test)^2, every operation one rounded float32 operation, the channels added
@@ -795,6 +795,33 @@ int rnerf_ssim_summary(const float* img0, const float* img1, int64_t n, int32_t 
  * larger than the image, a sheet of 2^31 bytes or more, an `out` that overlaps an input. */
 int rnerf_errmap_sheet(const float* reference, const float* test, int32_t H, int32_t W, int32_t K, const float* const* maps,
                        const int32_t* map_h, const int32_t* map_w, uint8_t* out, void* stream);
+
+/* ---- LPIPS (csrc/lpips.hip).  Appended; RNERF_VERSION stays 4 -------------------------------------------------------------------------
+ * rnerf_lpips: lpips.LPIPS(net='alex'), version 0.1, as metric/summary.py:63-68 calls it (model(ref, src, normalize=True)).  img0, img1:
+ * device float[n][H][W][3] in [0, 1], H, W >= 31 (below it AlexNet's second pool is empty).  x = 2 img - 1, then (x - shift) / scale per
+ * channel, shift = (-0.030, -0.088, -0.188), scale = (0.458, 0.448, 0.450); torchvision AlexNet `features` tapped after each ReLU: conv
+ * 3->64 k 11 s 4 p 2 | MaxPool 3/2, conv 64->192 k 5 p 2 | MaxPool 3/2, conv 192->384 k 3 p 1 | conv 384->256 k 3 p 1 | conv 256->256
+ * k 3 p 1 (cross-correlations, zero padding of the scaled input, floor pools).  Per tap l: f^ = f / (sqrt(sum_c f^2) + 1e-10),
+ * d_l = sum_c lin_l[c] (f^0 - f^1)^2.
+ * weights: device float[rnerf_lpips_weight_floats() = 2470848]: conv1.weight, conv1.bias, ..., conv5.weight, conv5.bias, lin0 .. lin4,
+ * each in torch's own layout ([Cout][Cin][kh][kw]; lin_l: [C_l]).  The kernels read this buffer as it is; nothing is packed.
+ * Outputs, each nullable but not all three:
+ *   value      float[n]: sum over l = 0..4 of mean(d_l) (spatial=False), fixed-order fp64 sums of per-workgroup partials, rounded once;
+ *   map        float[n][H][W]: sum over l = 0..4, in that order in float32, of d_l resized to H x W with torch's bilinear,
+ *              align_corners=False (spatial=True), unclipped (summary.py:67 clips to [0, 1] before colouring);
+ *   layer_maps float[n][P_0 + ... + P_4]: the five d_l of each pair back to back at their own resolutions P_l = h_l w_l,
+ *              h_0 = (H - 7) / 4 + 1, h_1 = ((h_0 - 3) / 2 + 1), h_2 = h_3 = h_4 = (h_1 - 3) / 2 + 1 (integer divisions), w likewise.
+ * The convolutions are implicit GEMMs in exact fp32 on the matrix cores (fp32 operands, fp32 accumulation, one k-ordered fused
+ * multiply-add chain per output); both images of a pair go through them as one batch.  No atomics: the same inputs give the same
+ * bytes, identical images give exactly 0, and swapping the images changes no byte.
+ * `workspace`: rnerf_lpips_workspace_bytes(n, H, W) bytes, 8-byte aligned, always needed (activations, d_l, partials; about 61 MB for
+ * one 800 x 800 pair).  The query returns 0 with the error set for n < 1, n > 65535, H or W < 31, or 2 n H W 3 >= 2^31.
+ * RNERF_ERR_ARG before any device work for the same, null img0 / img1 / weights / workspace, all three outputs null, a workspace that
+ * is not 8-byte aligned. */
+size_t rnerf_lpips_weight_floats(void);
+size_t rnerf_lpips_workspace_bytes(int64_t n, int32_t H, int32_t W);
+int rnerf_lpips(const float* img0, const float* img1, int64_t n, int32_t H, int32_t W, const float* weights, float* map, float* value,
+                float* layer_maps, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,7 @@ ABI_VERSION = 4          # == RNERF_VERSION of include/rnerf.h; load() refuses a
 NERFMLP_PARAMS = 595844
 BKGDMLP_PARAMS = 56963
 SO3MLP_PARAMS = 65411
+LPIPS_WEIGHT_FLOATS = 2470848      # rnerf_lpips_weight_floats()
 
 
 class RnerfError(RuntimeError):
@@ -188,6 +189,10 @@ SIGNATURES = {
     "rnerf_ssim_summary_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32, _i32, _i32]),
     "rnerf_ssim_summary": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp]),
     "rnerf_errmap_sheet": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), _vp, _vp]),
+    # LPIPS (csrc/lpips.hip)
+    "rnerf_lpips_weight_floats": (C.c_size_t, []),
+    "rnerf_lpips_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32]),
+    "rnerf_lpips": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -9,6 +9,8 @@ metric/compare.py:132-133,167-197; the masks come from mesh_mask.render_masks). 
 eval.py:175,196-198 (vis.visualize_suite: rnerf_vis_depth, rnerf_vis_normals) are computed for every view and written with save_output.
 With errmap=True every view also gets metric/summary.py's error maps, comparison sheet and numbers (errmap.error_maps, errmap.sheet:
 rnerf_errmap_mse, rnerf_ssim_summary, rnerf_flip, rnerf_errmap_sheet), scored on the 8-bit prediction as summary.py scores the PNG.
+With lpips=weights (lpips.load_weights) each view is also scored with LPIPS (utils.compute_lpips, rnerf_lpips; summary.py:63-68), and
+errmap=True then carries the LPIPS map and column as well.
 """
 from __future__ import annotations
 
@@ -53,10 +55,10 @@ def mask_suffix(mask_mode: Optional[str]) -> str:
     return "_crop" if mask_mode == "crop" else "_mask"
 
 
-def write_metric_files(out_dir: str, step, psnr_values, ssim_values, flip_values=None, suffix: str = "") -> None:
+def write_metric_files(out_dir: str, step, psnr_values, ssim_values, flip_values=None, suffix: str = "", lpips_values=None) -> None:
     """eval.py:207-215: psnrs_{step}.txt / ssims_{step}.txt (the values joined by spaces) and psnr.txt / ssim.txt (their means).  With
-    flip_values also flips_{step}.txt / flip.txt in the same style (not files of the reference).  suffix (mask_suffix) goes before
-    ".txt" in every name."""
+    flip_values also flips_{step}.txt / flip.txt in the same style (not files of the reference), with lpips_values lpips_{step}.txt /
+    lpips.txt.  suffix (mask_suffix) goes before ".txt" in every name."""
     with open(os.path.join(out_dir, f"psnrs_{step}{suffix}.txt"), "w") as f:
         f.write(" ".join([str(v) for v in psnr_values]))
     with open(os.path.join(out_dir, f"ssims_{step}{suffix}.txt"), "w") as f:
@@ -70,6 +72,11 @@ def write_metric_files(out_dir: str, step, psnr_values, ssim_values, flip_values
             f.write(" ".join([str(v) for v in flip_values]))
         with open(os.path.join(out_dir, f"flip{suffix}.txt"), "w") as f:
             f.write("{}".format(np.mean(np.array(flip_values))))
+    if lpips_values is not None:
+        with open(os.path.join(out_dir, f"lpips_{step}{suffix}.txt"), "w") as f:
+            f.write(" ".join([str(v) for v in lpips_values]))
+        with open(os.path.join(out_dir, f"lpips{suffix}.txt"), "w") as f:
+            f.write("{}".format(np.mean(np.array(lpips_values))))
 
 
 def apply_mask(pred_color: torch.Tensor, pixels: torch.Tensor, mask, mask_mode: str, min_size: int = 11):
@@ -95,7 +102,7 @@ def apply_mask(pred_color: torch.Tensor, pixels: torch.Tensor, mask, mask_mode: 
 def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192, normalize_disp: bool = False, out_dir: Optional[str] = None,
              step=None, save_output: bool = False, render_path: bool = False, flip: bool = False,
              flip_pixels_per_degree: Optional[float] = None, masks=None, mask_mode: Optional[str] = None, vis_suite: bool = False,
-             errmap: bool = False) -> dict:
+             errmap: bool = False, lpips=None) -> dict:
     """Render and score every view (eval.py:155-215).
 
     model / variables: what models.construct_nerf returns; views: batches as device_views yields them; rng: the render key (eval.py passes
@@ -129,7 +136,15 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
     view's one read-back.  With save_output the sheet is read back (one uint8 image per view) and errmap.write_error_maps writes
     errmap{suffix}/psnr_{idx:03d}.png, ssim_..., flip_... and errmap{suffix}/frame{suffix}/frame_{idx:03d}.png; after the loop
     metric_list{suffix}.txt and result{suffix}.txt (summary.py:243-250 without the LPIPS column).  Not with render_path (ValueError).
-    With errmap=False the keys, the files and the launches are those of the loop without it."""
+    With errmap=False the keys, the files and the launches are those of the loop without it.
+
+    lpips: a weights object (lpips.load_weights / lpips.from_tensors) also scores each view with utils.compute_lpips(pixels, pred_color,
+    lpips) on the same (masked and / or cropped) images: the result gains "lpips_values" and "lpips", save_output also writes
+    lpips_{step}{suffix}.txt and lpips{suffix}.txt; the float rides in the view's one read-back.  With errmap=True LPIPS is also scored
+    on the 8-bit prediction like the rest of the summary: "summary" gains "lpips_values" and "lpips", the clipped map (summary.py:67)
+    enters the sheet as the third of four maps (errmap.MAP_NAMES_LPIPS; the sheet is (2 + 4)(W + 5) wide), write_error_maps also writes
+    lpips_{idx:03d}.png, and metric_list / result carry the LPIPS column.  A view or crop below 31 x 31 is a ValueError.  With
+    lpips=None the keys, the files and the launches are those of the loop without it."""
     if errmap and render_path:
         raise ValueError("evaluate: errmap needs ground truth, render_path has none")
     if errmap:
@@ -146,8 +161,11 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
     def render_fn(key_0, key_1, rays, path=None):
         return model.apply(variables, key_0, key_1, rays, False, path=path)
 
-    psnr_values, ssim_values, flip_values = [], [], []
-    summary_values = ([], [], [])
+    psnr_values, ssim_values, flip_values, lpips_values = [], [], [], []
+    map_names = ()
+    if errmap:
+        map_names = em.MAP_NAMES_LPIPS if lpips is not None else em.MAP_NAMES
+    summary_values = {name: [] for name in map_names}
     num_rays = 0
     t0 = time.perf_counter()
     for idx, batch in enumerate(views):
@@ -172,20 +190,27 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
             scores = [psnr.to(torch.float32), ssim]
             if flip:
                 scores.append(utils.compute_flip(scored, pixels, flip_pixels_per_degree))
+            if lpips is not None:
+                if int(pixels.shape[0]) < ops.LPIPS_MIN_SIZE or int(pixels.shape[1]) < ops.LPIPS_MIN_SIZE:
+                    raise ValueError(f"evaluate: view {idx} is scored at {int(pixels.shape[0])} x {int(pixels.shape[1])} pixels, LPIPS needs at "
+                                     f"least {ops.LPIPS_MIN_SIZE} x {ops.LPIPS_MIN_SIZE}")
+                scores.append(utils.compute_lpips(pixels, scored, lpips))
             if errmap:
-                maps = em.error_maps(pixels, scored8)
-                sheet = em.sheet(pixels, scored8, [maps[name] for name in em.MAP_NAMES])
-                scores += [maps[name + "_value"] for name in em.MAP_NAMES]
+                maps = em.error_maps(pixels, scored8, lpips=lpips)
+                sheet = em.sheet(pixels, scored8, [maps[name] for name in map_names])
+                scores += [maps[name + "_value"] for name in map_names]
             pair = torch.stack(scores).cpu()                                  # the one read-back of the view: 8 bytes (12 with flip)
             psnr_values.append(float(pair[0]))
             ssim_values.append(float(pair[1]))
             if flip:
                 flip_values.append(float(pair[2]))
+            if lpips is not None:
+                lpips_values.append(float(pair[3 if flip else 2]))
             if errmap:
-                for values, v in zip(summary_values, pair[-3:]):
-                    values.append(float(v))
+                for name, v in zip(map_names, pair[-len(map_names):]):
+                    summary_values[name].append(float(v))
                 if save_output:
-                    em.write_error_maps(out_dir, idx, sheet, [tuple(maps[name].shape) for name in em.MAP_NAMES], suffix)
+                    em.write_error_maps(out_dir, idx, sheet, [tuple(maps[name].shape) for name in map_names], suffix)
         if save_output:
             utils.save_img(pred_color, os.path.join(out_dir, "{:03d}.png".format(idx)))
             utils.save_img(pred_disp[..., 0], os.path.join(out_dir, "disp_{:03d}.png".format(idx)))
@@ -199,9 +224,11 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
         torch.cuda.synchronize(pred_color.device)
     seconds = time.perf_counter() - t0
     if save_output and not render_path:
-        write_metric_files(out_dir, step, psnr_values, ssim_values, flip_values if flip else None, suffix)
-        if errmap and summary_values[0]:
-            em.write_summary_files(out_dir, *summary_values, suffix)
+        write_metric_files(out_dir, step, psnr_values, ssim_values, flip_values if flip else None, suffix,
+                           lpips_values if lpips is not None else None)
+        if errmap and summary_values["psnr"]:
+            em.write_summary_files(out_dir, summary_values["psnr"], summary_values["ssim"], summary_values["flip"], suffix,
+                                   summary_values.get("lpips"))
     have = bool(psnr_values)
     res = {"psnrs": psnr_values, "ssims": ssim_values,
            "psnr": float(np.mean(np.array(psnr_values))) if have else None,
@@ -210,10 +237,16 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
     if flip:
         res["flips"] = flip_values
         res["flip"] = float(np.mean(np.array(flip_values))) if flip_values else None
+    if lpips is not None:
+        res["lpips_values"] = lpips_values
+        res["lpips"] = float(np.mean(np.array(lpips_values))) if lpips_values else None
     if mask_mode is not None:
         res["mask_mode"] = mask_mode
     if errmap:
         mean = lambda v: float(np.mean(np.array(v))) if v else None
-        res["summary"] = {"psnrs": summary_values[0], "ssims": summary_values[1], "flips": summary_values[2],
-                          "psnr": mean(summary_values[0]), "ssim": mean(summary_values[1]), "flip": mean(summary_values[2])}
+        res["summary"] = {"psnrs": summary_values["psnr"], "ssims": summary_values["ssim"], "flips": summary_values["flip"],
+                          "psnr": mean(summary_values["psnr"]), "ssim": mean(summary_values["ssim"]), "flip": mean(summary_values["flip"])}
+        if lpips is not None:
+            res["summary"]["lpips_values"] = summary_values["lpips"]
+            res["summary"]["lpips"] = mean(summary_values["lpips"])
     return res

@@ -703,6 +703,72 @@ def flip(reference: torch.Tensor, test: torch.Tensor, *, pixels_per_degree: floa
     return out_map if return_map else mean
 
 
+LPIPS_MIN_SIZE = 31               # below it AlexNet's second pool is empty
+_lpips_workspaces: dict = {}      # (device index, stream) -> uint8 tensor: rnerf_lpips' workspace, kept and grown between calls
+
+
+def lpips_layer_shapes(H: int, W: int):
+    """The (h_l, w_l) of the five taps for an H x W image (include/rnerf.h, rnerf_lpips)."""
+    h0, w0 = (H - 7) // 4 + 1, (W - 7) // 4 + 1
+    h1, w1 = (h0 - 3) // 2 + 1, (w0 - 3) // 2 + 1
+    h2, w2 = (h1 - 3) // 2 + 1, (w1 - 3) // 2 + 1
+    return [(h0, w0), (h1, w1), (h2, w2), (h2, w2), (h2, w2)]
+
+
+def lpips(a: torch.Tensor, b: torch.Tensor, weights, return_both: bool = False, *, return_map: bool = False, return_layers: bool = False):
+    """lpips.LPIPS(net='alex') v0.1 with normalize=True (metric/summary.py:63-68) on the device (rnerf_lpips).  a, b: float32 device
+    tensors [..., H, W, 3] in [0, 1], H, W >= 31; weights: what lpips.load_weights / lpips.from_tensors return (or the flat float32
+    device tensor of rnerf_lpips_weight_floats() floats).  -> each pair's value, shape [...] (0-dim for [H, W, 3]); with return_map the
+    unclipped map [..., H, W]; with return_both (map, value) from the one call.  return_layers appends the five d_l as a list of
+    [..., h_l, w_l] views.  Issued on the current stream of the images' device; nothing is synchronised.  The workspace is kept per
+    device and stream and reused by later calls that fit in it."""
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"lpips: the images differ in shape: {tuple(a.shape)} vs {tuple(b.shape)}")
+    if a.dim() < 3 or int(a.shape[-1]) != 3:
+        raise ValueError(f"lpips: need [..., H, W, 3] images, got shape {tuple(a.shape)}")
+    if a.device != b.device:
+        raise ValueError(f"lpips: the images are on different devices ({a.device}, {b.device})")
+    *lead, H, W, _ = (int(s) for s in a.shape)
+    if H < LPIPS_MIN_SIZE or W < LPIPS_MIN_SIZE:
+        raise ValueError(f"lpips: LPIPS needs images of at least {LPIPS_MIN_SIZE} x {LPIPS_MIN_SIZE}, got {H} x {W}")
+    flat = getattr(weights, "flat", weights)
+    x, y, wt = _chk(a, "a"), _chk(b, "b"), _chk(flat, "weights")
+    if wt.numel() != _lib.LPIPS_WEIGHT_FLOATS:
+        raise _lib.RnerfError(f"lpips: the weights hold {wt.numel()} floats, not {_lib.LPIPS_WEIGHT_FLOATS}")
+    dev = x.device
+    if wt.device != dev:
+        raise ValueError(f"lpips: the weights are on {wt.device}, the images on {dev}")
+    n = 1
+    for s in lead:
+        n *= s
+    if n == 0:
+        raise ValueError(f"lpips: empty batch, shape {tuple(a.shape)}")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nb = lib.rnerf_lpips_workspace_bytes(n, H, W)
+        if nb == 0:
+            check(-1, "rnerf_lpips_workspace_bytes")
+        key = (dev.index, stream)
+        ws = _lpips_workspaces.get(key)
+        if ws is None or ws.numel() < nb:
+            ws = _lpips_workspaces[key] = torch.empty(nb, dtype=torch.uint8, device=dev)
+        want_map = return_map or return_both
+        out_map = torch.empty(tuple(lead) + (H, W), dtype=torch.float32, device=dev) if want_map else None
+        value = torch.empty(tuple(lead), dtype=torch.float32, device=dev) if return_both or not return_map else None
+        shapes = lpips_layer_shapes(H, W)
+        layers = torch.empty((n, sum(h * w for h, w in shapes)), dtype=torch.float32, device=dev) if return_layers else None
+        check(lib.rnerf_lpips(ptr(x), ptr(y), n, H, W, ptr(wt), ptr(out_map), ptr(value), ptr(layers), ptr(ws), stream), "rnerf_lpips")
+    res = (out_map, value) if return_both else (out_map if return_map else value)
+    if not return_layers:
+        return res
+    views, at = [], 0
+    for h, w in shapes:
+        views.append(layers[:, at:at + h * w].reshape(tuple(lead) + (h, w)))
+        at += h * w
+    return (res + (views,)) if return_both else (res, views)
+
+
 def _image_pair(a: torch.Tensor, b: torch.Tensor, what: str):
     if tuple(a.shape) != tuple(b.shape):
         raise ValueError(f"{what}: the images differ in shape: {tuple(a.shape)} vs {tuple(b.shape)}")

@@ -146,6 +146,28 @@ def compute_flip(reference, test, pixels_per_degree=None, return_map=False):
     return ops.flip(as_f32(reference), as_f32(test), pixels_per_degree=ppd, return_map=return_map)
 
 
+def compute_lpips(img0, img1, weights, return_map=False):
+    """LPIPS, lpips.LPIPS(net='alex') v0.1 with normalize=True (metric/summary.py:63-68), on the device (ops.lpips -> rnerf_lpips).
+
+    img0, img1: torch tensors or numpy arrays of one shape [H, W, 3] or [n, H, W, 3] (channels last, in [0, 1], H, W >= 31); a numpy (or
+    CPU) argument is uploaded to the device of the weights.  weights: lpips.load_weights / lpips.from_tensors.  Returns a device tensor:
+    each pair's value (0-dim for one pair: summary.py:68) or, with return_map, the unclipped map [..., H, W] (summary.py:66 before its
+    clip).  Nothing is synchronised.  There is no CPU fallback."""
+    s0, s1 = tuple(np.shape(img0)), tuple(np.shape(img1))
+    if s0 != s1:
+        raise ValueError(f"compute_lpips: the images differ in shape: {s0} vs {s1}")
+    if len(s0) not in (3, 4) or s0[-1] != 3:
+        raise ValueError(f"compute_lpips: need [H, W, 3] or [n, H, W, 3] images, got shape {s0}")
+    dev = weights.device
+
+    def as_f32(t):
+        if not isinstance(t, torch.Tensor):
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float32)))
+        return t.to(device=dev, dtype=torch.float32)
+    from . import ops
+    return ops.lpips(as_f32(img0), as_f32(img1), weights, return_map=return_map)
+
+
 def save_img(img, pth, to8b=True):
     """rnerf/utils.py:474-488: a PNG of `img` ([H, W] or [H, W, C]); with to8b the values are clipped to [0, 1] and scaled by 255, the
     cast to uint8 truncating.  Accepts a device tensor (read back here) or a numpy array."""
