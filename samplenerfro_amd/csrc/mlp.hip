@@ -1181,7 +1181,9 @@ __global__ void nerfmlp_pack_bwd_kernel(const float* __restrict__ params, char* 
 
 // dgrad twin of PrevConv: the B operands of k-step S of the NEXT dgrad GEMM = (state / WSCALE [+ d sigma * w_sigma]) * ReLU mask, split
 // into 16-bit hi/lo parts, computed pair by pair in the shadow of the current k-step's MFMAs.
-template <int PREC, int S, bool NEED_LO, bool ONE = false>
+// SEAM: k-step 0 of a layer, converted by DgradSeam in the previous layer's last k-step.  Its d sigma term keeps the form k-step 0 has
+// always had, fma(d sigma, w, state / WSCALE) — one rounding, where the steady k-steps round d sigma * w first — taken by a select.
+template <int PREC, int S, bool NEED_LO, bool ONE = false, bool SEAM = false>
 struct GradConv {
   using PP = Prec<PREC>;
   const f32x16& p0;   // m-tile 0 state (accumulator registers of the previous dgrad layer)
@@ -1190,6 +1192,8 @@ struct GradConv {
   uint32_t w0, w1;    // mask word S>>2 of both m-tiles (all ones: no ReLU)
   uint32_t hi[2][4], lo[2][4];
   float x0, x1;
+  bool wadd;          // SEAM: the layer receives d sigma (gw0 / gw1 of the two m-tiles) times the sigma weights wv of these 8 features
+  float gw0, gw1, wv[8];
   __device__ __forceinline__ GradConv(const f32x16& p) : p0(p) {}
   template <int C, int PI>
   __device__ __forceinline__ void chunk() {
@@ -1199,8 +1203,15 @@ struct GradConv {
     if constexpr (C == 0) {
       const float r0 = mt == 0 ? p0[8 * (S & 1) + 2 * p] : v1[2 * p];
       const float r1 = mt == 0 ? p0[8 * (S & 1) + 2 * p + 1] : v1[2 * p + 1];
-      x0 = fmaf(r0, INV_SCALE, mt == 0 ? t0[2 * p] : t1[2 * p]);
-      x1 = fmaf(r1, INV_SCALE, mt == 0 ? t0[2 * p + 1] : t1[2 * p + 1]);
+      if constexpr (SEAM) {
+        const float gw = mt == 0 ? gw0 : gw1;
+        x0 = r0 * INV_SCALE; x1 = r1 * INV_SCALE;
+        x0 = wadd ? fmaf(gw, wv[2 * p], x0) : x0;
+        x1 = wadd ? fmaf(gw, wv[2 * p + 1], x1) : x1;
+      } else {
+        x0 = fmaf(r0, INV_SCALE, mt == 0 ? t0[2 * p] : t1[2 * p]);
+        x1 = fmaf(r1, INV_SCALE, mt == 0 ? t0[2 * p + 1] : t1[2 * p + 1]);
+      }
     } else if constexpr (C == 1) {
       const uint32_t w = mt == 0 ? w0 : w1;      // v_bfe_i32 spreads the flag into a 0 / ~0 word, v_and applies it: 2 ops per value
       constexpr int pos0 = 8 * (S & 3) + p, pos1 = pos0 + 4;
@@ -1228,6 +1239,43 @@ struct GradConv {
     if constexpr (ONE) { o.h1 = o.h0; o.l1 = o.l0; }
     else { o.h1 = make_uint4(hi[1][0], hi[1][1], hi[1][2], hi[1][3]); o.l1 = make_uint4(lo[1][0], lo[1][1], lo[1][2], lo[1][3]); }
     return o;
+  }
+};
+
+// dgrad twin of SeamWork: the work of a dgrad layer's LAST k-step, in the shadow of its MFMAs.  Once the MFMAs of tile t are issued, tile
+// t - 1 is final: in tile t's slots its m-tile 0 state moves to prev0[t - 1] and its m-tile 1 state to the wave's LDS state (both are dead
+// by then: the last k-step's operands were converted a k-step earlier), and pair t - 1 of the NEXT layer's k-step 0 is converted from
+// tile 0 (cv; its mask word was loaded a layer ahead, its sigma weights two k-steps ahead).  Tile 7 is handed over by finish().
+template <int PREC, bool NEED_LO, bool ONE = false>
+struct DgradSeam {
+  f32x16 (&acc0)[8];
+  f32x16 (&acc1)[8];
+  f32x16 (&prev0)[8];
+  float4* st1;
+  GradConv<PREC, 0, NEED_LO, ONE, true> cv;      // pairs 0..3: m-tile 0 from acc0[0], pairs 4..7: m-tile 1 from acc1[0]
+  __device__ __forceinline__ DgradSeam(f32x16 (&a0)[8], f32x16 (&a1)[8], f32x16 (&p0)[8], float4* s1) : acc0(a0), acc1(a1), prev0(p0), st1(s1), cv(a0[0]) {}
+  template <int C, int T>
+  __device__ __forceinline__ void move() {            // piece C of the hand-over of tile T
+    if constexpr (C == 0) prev0[T] = acc0[T];
+    else if constexpr (!ONE) st1[(T * 4 + C - 1) * 64] = make_float4(acc1[T][4 * (C - 1)], acc1[T][4 * (C - 1) + 1], acc1[T][4 * (C - 1) + 2], acc1[T][4 * (C - 1) + 3]);
+  }
+  template <int C, int Q>
+  __device__ __forceinline__ void conv() {
+    if constexpr (ONE && Q >= 4) return;
+    if constexpr (C == 0 && Q >= 4) { cv.v1[2 * (Q & 3)] = acc1[0][2 * (Q & 3)]; cv.v1[2 * (Q & 3) + 1] = acc1[0][2 * (Q & 3) + 1]; }
+    cv.template chunk<C, Q>();
+  }
+  template <int C, int PI>
+  __device__ __forceinline__ void chunk() {
+    if constexpr (PI >= 1) {
+      move<C, PI - 1>();
+      conv<C, PI - 1>();
+      // pair 7 after pair 6 (GradConv keeps ONE pair in flight: x0 / x1)
+      if constexpr (PI == 7 && C == 4) { conv<0, 7>(); conv<1, 7>(); conv<2, 7>(); conv<3, 7>(); conv<4, 7>(); }
+    }
+  }
+  __device__ __forceinline__ void finish() {
+    move<0, 7>(); move<1, 7>(); move<2, 7>(); move<3, 7>(); move<4, 7>();
   }
 };
 
@@ -1269,7 +1317,6 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
   float4* __restrict__ st1 = (float4*)(smem + 2 * SLAB + wave * 32768) + lane;
   int buf = 0;
   size_t off = 0;
-  NoWork nowork;
 
   if ((int)blockIdx.x < n_tiles) { issue_slab<SLAB>(packed_bwd, 0u, wave, lane); off = SLAB; }
   slab_wait_dma();
@@ -1280,6 +1327,22 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
     const bool has_next_tile = tile + (int)gridDim.x < n_tiles;
     const long long srow0 = (long long)tile * TROWS + wave * WROWS + m;
     const long long t32_0 = (long long)tile * (TROWS / 32) + wave * (WROWS / 32);
+    // An opaque per-tile copy of the aux base, as in the forward (auxt there): left alone, hipcc hoists the tile-invariant head and sigma
+    // weight loads in front of the tile loop — 64 vectors loaded one by one, each waited for and spilled, and reloaded in every tile.
+    const float* __restrict__ auxt = fwd_aux;
+    asm volatile("" : "+s"(auxt));
+    // rgb-head weights (Dense_11, [3][128]) of the 8 features this lane holds in each register group of n-tile t: 12 vectors per n-tile,
+    // fetched as one batch — n-tile 0 here, beside the d raw read, n-tile t + 1 while n-tile t is formed
+    const float* __restrict__ hw = auxt + AUX_WRGB + 4 * h;
+    auto head_load = [&](int t, float4 (&W)[12]) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int n = 32 * t + 8 * q;
+        W[3 * q] = gload4(hw + n); W[3 * q + 1] = gload4(hw + 128 + n); W[3 * q + 2] = gload4(hw + 256 + n);
+      }
+    };
+    float4 Wc[12];
+    head_load(0, Wc);
     float4 g[2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
@@ -1302,6 +1365,8 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
       }
     }
     f32x16 acc0[8], acc1[8], prev0[8];
+    float4 wna = make_float4(0.f, 0.f, 0.f, 0.f), wnb = wna, wk0a = wna, wk0b = wna;      // sigma weights in flight, see RNERF_DG_KSTEP
+    KOps cur;                                   // operands of the next k-step; across a layer seam: k-step 0 of the next layer (DgradSeam)
 
     auto dy_store = [&](int q, const KOps& o) {
       uint4* dst = dy + dy_addr(q, t32_0, m, h);
@@ -1328,7 +1393,9 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
 #undef RNERF_NTL
     };
     // operands of k-step s from the state (prev0 / st1): x = (state + dsig * wadd) * 1[mask != 0]
-    auto grad_ops = [&](int s, bool use_mask, const uint4 mk0, const uint4 mk1, const float* __restrict__ wadd) -> KOps {
+    // (wadd: add d sigma * w_sigma, the 8 sigma weights of this lane's features given in wa / wb)
+    auto grad_ops = [&](int s, bool use_mask, const uint4 mk0, const uint4 mk1, bool wadd, const float4 wa, const float4 wb) -> KOps {
+      const float wv[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
       float r1[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       if constexpr (!ONE) {
         const float4 u0 = st1[((s >> 1) * 4 + 2 * (s & 1)) * 64], u1 = st1[((s >> 1) * 4 + 2 * (s & 1) + 1) * 64];
@@ -1340,7 +1407,7 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float a = prev0[s >> 1][8 * (s & 1) + j] * INV_SCALE, b = r1[j] * INV_SCALE;
-        if (wadd) { const float w = wadd[16 * s + 8 * (j >> 2) + 4 * h + (j & 3)]; a = fmaf(g[0].w, w, a); b = fmaf(g[1].w, w, b); }
+        if (wadd) { const float w = wv[j]; a = fmaf(g[0].w, w, a); b = fmaf(g[1].w, w, b); }
         if (use_mask) {
           const uint32_t bit = 1u << (8 * (s & 3) + (j >> 1) + 4 * (j & 1));
           a = (w0 & bit) ? a : 0.f;
@@ -1382,18 +1449,32 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
       if constexpr (ONE) { o.h1 = o.h0; o.l1 = o.l0; } else split8<PREC>(hz1, o.h1, o.l1);
       dy_store(DY_HEADS, o);
 #pragma unroll
-      for (int t = 0; t < 8; ++t)
+      for (int t = 0; t < 4; ++t) {       // register r of n-tile t is feature n = 32 t + 8 (r >> 2) + 4 h + (r & 3)
+        float4 Wn[12];
+        if (t + 1 < 4) head_load(t + 1, Wn);
+        RNERF_PIN();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 vr = Wc[3 * q], vg = Wc[3 * q + 1], vb = Wc[3 * q + 2];
+          const float wrv[4] = {vr.x, vr.y, vr.z, vr.w}, wgv[4] = {vg.x, vg.y, vg.z, vg.w}, wbv[4] = {vb.x, vb.y, vb.z, vb.w};
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float wr = wrv[i], wg = wgv[i], wb = wbv[i];
+            acc0[t][4 * q + i] = (g[0].x * wr + g[0].y * wg + g[0].z * wb) * PP::WSCALE;       // the state is kept in the accumulators' units (x WSCALE)
+            if constexpr (!ONE) acc1[t][4 * q + i] = (g[1].x * wr + g[1].y * wg + g[1].z * wb) * PP::WSCALE;
+          }
+        }
+        if (t + 1 < 4) {
+#pragma unroll
+          for (int q = 0; q < 12; ++q) Wc[q] = Wn[q];
+        }
+      }
+#pragma unroll
+      for (int t = 4; t < 8; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          float a = 0.f, b = 0.f;
-          if (t < 4) {
-            const int n = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
-            const float wr = fwd_aux[AUX_WRGB + n], wg = fwd_aux[AUX_WRGB + 128 + n], wb = fwd_aux[AUX_WRGB + 256 + n];
-            a = (g[0].x * wr + g[0].y * wg + g[0].z * wb) * PP::WSCALE;       // the state is kept in the accumulators' units (x WSCALE)
-            b = (g[1].x * wr + g[1].y * wg + g[1].z * wb) * PP::WSCALE;
-          }
-          acc0[t][r] = a;
-          if constexpr (!ONE) acc1[t][r] = b;
+          acc0[t][r] = 0.f;
+          if constexpr (!ONE) acc1[t][r] = 0.f;
         }
       layer_end();
     }
@@ -1402,10 +1483,15 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
     {
       uint4 ma, mb;
       mask_at(8, ma, mb);
-      KOps cur = grad_ops(0, true, ma, mb, nullptr);
+      cur = grad_ops(0, true, ma, mb, false, wk0a, wk0b);
+      // sigma weights: the two vectors of k-step S + 2 are fetched in k-step S (the k-step's closing wait covers them), whether the layer
+      // takes d sigma or not (wl: the sigma weights for layer 7, else the aux zeros; wl_next: the same for the layer after this one) —
+      // wna / wnb hold those of k-step S + 1, wk0a / wk0b those of the next layer's k-step 0
 #define RNERF_DG_KSTEP(S, NSTEPS, SLOT0, PREFETCH_STMT)                                                                       \
       {                                                                                                                         \
         dy_store((SLOT0) + S, cur);                                                                                             \
+        const float* __restrict__ wsrc = (S + 2 < NSTEPS) ? wl + 16 * (S + 2) : wl_next + 16 * (S + 2 - NSTEPS);                \
+        const float4 wfa = gload4(wsrc), wfb = gload4(wsrc + 8);                                                                \
         auto dma = [&]() { PREFETCH_STMT; };   /* issued after the first two tiles' MFMAs (an LDS-DMA instruction costs ~100 issue cycles) */ \
         if constexpr (S + 1 < NSTEPS) {                                                                                         \
           GradConv<PREC, S + 1, NEED_LO, ONE> cv(prev0[(S + 1) >> 1]);                                                                   \
@@ -1413,9 +1499,8 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
             const float4 u0 = st1[(((S + 1) >> 1) * 4 + 2 * ((S + 1) & 1)) * 64], u1 = st1[(((S + 1) >> 1) * 4 + 2 * ((S + 1) & 1) + 1) * 64]; \
             cv.v1[0] = u0.x; cv.v1[1] = u0.y; cv.v1[2] = u0.z; cv.v1[3] = u0.w; cv.v1[4] = u1.x; cv.v1[5] = u1.y; cv.v1[6] = u1.z; cv.v1[7] = u1.w; \
           }                                                                                                                     \
-          if (wadd) {   /* ONE test per k-step (per value it was 8 branches), two vector loads; only layer 7 takes it */         \
-            const float4 wa = *(const float4*)(wadd + 16 * (S + 1) + 4 * h), wb = *(const float4*)(wadd + 16 * (S + 1) + 8 + 4 * h); \
-            const float wv[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};                                               \
+          if (wadd) {   /* ONE test per k-step (per value it was 8 branches); only layer 7 takes it */                          \
+            const float wv[8] = {wna.x, wna.y, wna.z, wna.w, wnb.x, wnb.y, wnb.z, wnb.w};                                       \
             _Pragma("unroll") for (int j = 0; j < 8; ++j) { cv.t0[j] = g[0].w * wv[j]; cv.t1[j] = g[1].w * wv[j]; }             \
           } else {                                                                                                              \
             _Pragma("unroll") for (int j = 0; j < 8; ++j) { cv.t0[j] = 0.f; cv.t1[j] = 0.f; }                                   \
@@ -1424,19 +1509,28 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
           cv.w1 = ((S + 1) >> 2) == 0 ? mb.x : (((S + 1) >> 2) == 1 ? mb.y : (((S + 1) >> 2) == 2 ? mb.z : mb.w));             \
           kstep_mfma<PREC, 8, 0, S == 0, GradConv<PREC, S + 1, NEED_LO, ONE>, decltype(dma), DGP>(acc0, acc1, cur, smem + buf * SLAB, lane, cv, dma); \
           cur = cv.result();                                                                                                    \
-        } else {                                                                                                                \
-          kstep_mfma<PREC, 8, 0, false, NoWork, decltype(dma), DGP>(acc0, acc1, cur, smem + buf * SLAB, lane, nowork, dma);         \
+        } else {   /* the layer seam: hand the state over and convert the next layer's k-step 0 (seam_w0 / seam_w1: its mask words) */  \
+          DgradSeam<PREC, NEED_LO, ONE> seam(acc0, acc1, prev0, st1);                                                           \
+          seam.cv.w0 = seam_w0; seam.cv.w1 = seam_w1; seam.cv.wadd = seam_wadd; seam.cv.gw0 = g[0].w; seam.cv.gw1 = g[1].w;     \
+          seam.cv.wv[0] = wk0a.x; seam.cv.wv[1] = wk0a.y; seam.cv.wv[2] = wk0a.z; seam.cv.wv[3] = wk0a.w;                       \
+          seam.cv.wv[4] = wk0b.x; seam.cv.wv[5] = wk0b.y; seam.cv.wv[6] = wk0b.z; seam.cv.wv[7] = wk0b.w;                       \
+          kstep_mfma<PREC, 8, 0, false, DgradSeam<PREC, NEED_LO, ONE>, decltype(dma), DGP>(acc0, acc1, cur, smem + buf * SLAB, lane, seam, dma); \
+          seam.finish();                                                                                                        \
+          cur = seam.cv.result();                                                                                               \
         }                                                                                                                       \
+        if constexpr (S + 2 == NSTEPS) { wk0a = wfa; wk0b = wfb; } else { wna = wfa; wnb = wfb; }                               \
         SLAB_DONE();                                                                                                            \
       }
       {
-        const float* __restrict__ wadd = nullptr;
+        constexpr bool wadd = false, seam_wadd = false;
+        constexpr uint32_t seam_w0 = ~0u, seam_w1 = ~0u;      // layer 8, the bottleneck, has no ReLU
+        const float* __restrict__ wl = auxt + AUX_ZERO + 4 * h;
+        const float* __restrict__ wl_next = wl;
         RNERF_DG_KSTEP(0, 8, DY_L9, SLAB_PREFETCH(true)) RNERF_DG_KSTEP(1, 8, DY_L9, SLAB_PREFETCH(true))
         RNERF_DG_KSTEP(2, 8, DY_L9, SLAB_PREFETCH(true)) RNERF_DG_KSTEP(3, 8, DY_L9, SLAB_PREFETCH(true))
         RNERF_DG_KSTEP(4, 8, DY_L9, SLAB_PREFETCH(true)) RNERF_DG_KSTEP(5, 8, DY_L9, SLAB_PREFETCH(true))
         RNERF_DG_KSTEP(6, 8, DY_L9, SLAB_PREFETCH(true)) RNERF_DG_KSTEP(7, 8, DY_L9, SLAB_PREFETCH(true))
       }
-      layer_end();
     }
 
     // ---- dgrad of MFMA layers 8..1: dY_l = (dX_{l+1} [+ d sigma * w_sigma for l = 7]) * 1[X_{l+1} > 0]  (no mask for the bottleneck l = 8)
@@ -1444,11 +1538,14 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
 #pragma unroll 1
     for (int l = 8; l >= 1; --l) {
       const bool use_mask = l != 8;
-      const float* __restrict__ wadd = (l == 7) ? fwd_aux + AUX_WSIG : nullptr;
+      const bool wadd = l == 7;
+      const float* __restrict__ wl = auxt + (l == 7 ? AUX_WSIG : AUX_ZERO) + 4 * h;
+      const float* __restrict__ wl_next = auxt + (l == 8 ? AUX_WSIG : AUX_ZERO) + 4 * h;
       uint4 ma = nma, mb = nmb;                  // set l = the ReLU mask of the input of layer l+1
       if (!use_mask) { ma = make_uint4(~0u, ~0u, ~0u, ~0u); mb = ma; }
       mask_at(l - 1, nma, nmb);
-      KOps cur = grad_ops(0, true, ma, mb, wadd);
+      const bool seam_wadd = l == 8;             // the seam converts k-step 0 of layer l - 1 (l = 1: of the dY_0 record)
+      const uint32_t &seam_w0 = nma.x, &seam_w1 = nmb.x;
       const int slot0 = 16 * l;
 #define RNERF_DG_PF(S) do { if ((S) == 15 && l == 1) { if (has_next_tile) off = 0; SLAB_PREFETCH(has_next_tile); } else SLAB_PREFETCH(true); } while (0)
       RNERF_DG_KSTEP(0, 16, slot0, RNERF_DG_PF(0)) RNERF_DG_KSTEP(1, 16, slot0, RNERF_DG_PF(1)) RNERF_DG_KSTEP(2, 16, slot0, RNERF_DG_PF(2))
@@ -1458,14 +1555,14 @@ nerfmlp_dgrad_kernel(const char* __restrict__ packed_bwd, const float* __restric
       RNERF_DG_KSTEP(12, 16, slot0, RNERF_DG_PF(12)) RNERF_DG_KSTEP(13, 16, slot0, RNERF_DG_PF(13)) RNERF_DG_KSTEP(14, 16, slot0, RNERF_DG_PF(14))
       RNERF_DG_KSTEP(15, 16, slot0, RNERF_DG_PF(15))
 #undef RNERF_DG_PF
-      layer_end();
     }
 #undef RNERF_DG_KSTEP
 
-    // ---- dY_0 = dX_1 * 1[X_1 > 0]: only recorded (layer 0's inputs are constants)
+    // ---- dY_0 = dX_1 * 1[X_1 > 0]: only recorded (layer 0's inputs are constants); k-step 0 comes from Dense_1's seam
+    dy_store(0, cur);
 #pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const KOps o = grad_ops(s, true, nma, nmb, nullptr);
+    for (int s = 1; s < 16; ++s) {
+      const KOps o = grad_ops(s, true, nma, nmb, false, wk0a, wk0b);
       dy_store(s, o);
     }
 #undef SLAB_PREFETCH
