@@ -38,7 +38,8 @@ extern "C" {
  * 4: the opt-in schedule fields no caller set are gone.  rnerf_train_cfg ends with aux_stream, grads_stream (nothing in between);
  * rnerf_prefetch ends with side_stream (the march always forks right before the last NerfMLP wgrad); rnerf_bkgd_backward is the only
  * background-MLP backward entry point.  Still 4 with rnerf_flip / rnerf_flip_workspace_bytes, rnerf_visual_hull_*, rnerf_marching_cubes_*,
- * rnerf_mesh_depth, rnerf_mask_dilate, rnerf_vis_*, rnerf_images_prepare, rnerf_errmap_* and rnerf_ssim_summary: they are appended, no
+ * rnerf_mesh_depth, rnerf_mask_dilate, rnerf_vis_*, rnerf_images_prepare, rnerf_errmap_*, rnerf_ssim_summary, rnerf_lpips and
+ * rnerf_components_*: they are appended, no
  * existing entry point or struct moved. */
 #define RNERF_VERSION 4
 
@@ -822,6 +823,34 @@ size_t rnerf_lpips_weight_floats(void);
 size_t rnerf_lpips_workspace_bytes(int64_t n, int32_t H, int32_t W);
 int rnerf_lpips(const float* img0, const float* img1, int64_t n, int32_t H, int32_t W, const float* weights, float* map, float* value,
                 float* layer_maps, void* workspace, void* stream);
+
+/* ---- Connected components of a voxel grid (csrc/components.hip).  Appended; RNERF_VERSION stays 4 ------------------------------------
+ * What the reference's README leaves to Blender ("remove the noisy components in the proxy geometry"): the floaters of a carved hull, of
+ * a voxelised proxy mesh and of a trained density.  Grids are [X][Y][Z], z fastest, linear index x Y Z + y Z + z (the reference's flat
+ * order); every dims[a] >= 1 and X Y Z <= 2^31 - 1, so that a label fits an int32.  All pointers are device pointers except dims.
+ *   rnerf_components_label: solid uint8[X Y Z] (non-zero = solid); phase 1 labels the solid voxels, 0 the empty ones; connectivity 6
+ *     (faces), 18 (faces and edges) or 26 (faces, edges and corners).  labels int32[X Y Z]: for a voxel of the labelled phase the smallest
+ *     linear index in its component, -1 for every other voxel.  That is a pure function of the input: the same bytes on every run.
+ *     Union-find with atomicMin hooking in three launches whatever the grid holds (8 x 8 x 64 tiles in LDS; tile faces, edges and corners
+ *     with agent-scope atomics; flatten), nothing read back.  Every find / union loop is bounded by construction (parents only decrease)
+ *     and has an iteration cap all the same; a kernel that reaches it sets word 0 of `workspace` (int32, zeroed by this call) and leaves:
+ *     the labels are then not valid.  `workspace`: rnerf_components_workspace_bytes(dims) bytes, 4-byte aligned.
+ *   rnerf_components_stats: from such labels, size int32[X Y Z] = the component's voxel count at its root index and 0 elsewhere, border
+ *     uint8[X Y Z] = 1 at the root if a voxel of the component lies on one of the six faces of the grid and 0 elsewhere, counts int64[2] =
+ *     {components, labelled voxels}.  All three are zeroed by the call.  Integer atomics after a per-wave reduction: exact.
+ *   rnerf_components_apply: one launch over `grid` (dtype RNERF_COMPONENTS_U8 / _I32 / _F32, [X Y Z]): a voxel with labels[i] = r >= 0
+ *     and keep[r] == 0 becomes drop_value; then one with fill_labels[i] = r >= 0 and fill[r] != 0 becomes fill_value; everything else is
+ *     left as it is.  keep, fill: uint8[X Y Z] read at root indices.  Either pair (labels, keep) / (fill_labels, fill) may be null, not
+ *     both.  The values are converted from double to the grid's type.
+ * RNERF_ERR_ARG before any device work for null pointers, a dimension < 1, X Y Z >= 2^31 (the workspace query then returns 0 with the
+ * message), a phase other than 0 / 1, a connectivity other than 6 / 18 / 26, an unknown dtype, a misaligned pointer. */
+enum rnerf_components_dtype { RNERF_COMPONENTS_U8 = 0, RNERF_COMPONENTS_I32 = 1, RNERF_COMPONENTS_F32 = 2 };
+size_t rnerf_components_workspace_bytes(const int32_t dims[3]);
+int rnerf_components_label(const uint8_t* solid, const int32_t dims[3], int32_t phase, int32_t connectivity, int32_t* labels,
+                           void* workspace, void* stream);
+int rnerf_components_stats(const int32_t* labels, const int32_t dims[3], int32_t* size, uint8_t* border, int64_t* counts, void* stream);
+int rnerf_components_apply(const int32_t* labels, const uint8_t* keep, double drop_value, const int32_t* fill_labels, const uint8_t* fill,
+                           double fill_value, void* grid, int32_t dtype, const int32_t dims[3], void* stream);
 
 #ifdef __cplusplus
 }

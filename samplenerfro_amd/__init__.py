@@ -11,7 +11,7 @@ __all__ = ["Rays", "Stats", "default_flags", "render_image", "prng", "utils"]
 
 def __getattr__(name):
     # models/ops import torch lazily so that `import samplenerfro_amd` stays cheap for symbol checks
-    if name in ("models", "ops", "synthetic", "grid", "train", "distributed", "evaluate", "visual_hull", "voxelize", "marching_cubes", "extract", "mesh_mask", "vis"):
+    if name in ("models", "ops", "synthetic", "grid", "train", "distributed", "evaluate", "visual_hull", "voxelize", "marching_cubes", "extract", "mesh_mask", "vis", "components"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -193,6 +193,11 @@ SIGNATURES = {
     "rnerf_lpips_weight_floats": (C.c_size_t, []),
     "rnerf_lpips_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32]),
     "rnerf_lpips": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # connected components (csrc/components.hip)
+    "rnerf_components_workspace_bytes": (C.c_size_t, [C.POINTER(_i32 * 3)]),
+    "rnerf_components_label": (C.c_int, [_vp, C.POINTER(_i32 * 3), _i32, _i32, _vp, _vp, _vp]),
+    "rnerf_components_stats": (C.c_int, [_vp, C.POINTER(_i32 * 3), _vp, _vp, _vp, _vp]),
+    "rnerf_components_apply": (C.c_int, [_vp, _vp, _dbl, _vp, _vp, _dbl, _vp, _i32, C.POINTER(_i32 * 3), _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -34,10 +34,19 @@ def alpha_grid(model, variables, resolution: int = 256, range: float = 1.2, chun
     return out.reshape(N + 1, N + 1, N + 1)
 
 
-def extract_mesh(model, variables, resolution: int = 256, range: float = 1.2, threshold: float = 0.1, chunk: int = 1 << 18, device=None):
+def extract_mesh(model, variables, resolution: int = 256, range: float = 1.2, threshold: float = 0.1, chunk: int = 1 << 18, device=None,
+                 keep=None, min_voxels: int = 1, connectivity: int = 6):
     """extract_mesh.py:232-268 (flags :40-42): alpha_grid -> marching cubes at `threshold` -> world coordinates.
-    -> (verts float64 [V,3] within [-range, range]^3, faces int32 [F,3]) on the device."""
+    -> (verts float64 [V,3] within [-range, range]^3, faces int32 [F,3]) on the device.
+    keep / min_voxels / connectivity: components.select's rules on alpha > threshold (float64, marching cubes' own test); the alpha of
+    dropped samples is 0 before marching cubes, so the floaters of the density leave no crumbs.  keep=None, min_voxels=1: nothing is done."""
+    from . import components
+    components._check_selection(keep, min_voxels, connectivity)
     grid = alpha_grid(model, variables, resolution, range, chunk, device)
+    if keep is not None or int(min_voxels) > 1:
+        grid = grid.detach().to(torch.float32).clone().contiguous()
+        solid = (grid.to(torch.float64) > float(threshold)).to(torch.uint8)
+        components.clean_grids(solid, [(grid, 0.0, 0.0)], keep, min_voxels, connectivity, False)
     verts, faces = mc.marching_cubes(grid, threshold)
     den = torch.full((3,), float(int(resolution)), dtype=torch.float64, device=verts.device)      # a tensor: a true division
     return verts / den * (2.0 * range) - range, faces

@@ -2,6 +2,7 @@
 
     data, ndim, nmin, nmax = from_calib(calib, masks, num_voxels=512, device="cuda:0")     # calib = json.load(open("calib.json"))
     data, ndim, nmin, nmax, count = carve(masks, cam_mat, transforms, 512, return_count=True)
+    data, count, info = clean(count, len(transforms), 0.9, keep=1)    # drop the floaters, fill enclosed cavities (components.py)
     save_mesh_pkl(path, count, len(transforms), 0.9, nmin, nmax)      # the dict train.py:209-217 / grid.load_mesh_pkl read
     verts, faces = preview_mesh(count, len(transforms), 0.9, nmin, nmax, out_dir=".")     # mesh_{G}_0_{threshold}.obj
 
@@ -85,11 +86,47 @@ def _masks_uint8(masks):
     return m
 
 
+def clean(count, num_views: int, threshold: float = 0.9, keep: Optional[int] = 1, min_voxels: int = 1, connectivity: int = 6,
+          fill_holes: bool = True, ior_inside: float = 1.33, ior_outside: float = 1.0):
+    """The hull without its floaters: what the reference's README leaves to Blender before voxelising ("remove the noisy components in the
+    proxy geometry").  The clamped projections (:129-130) let voxels far outside every frustum vote with the masks' edges, so a carved
+    grid regularly holds loose parts beside the object.  -> (data float32 [G,G,G], count_clean int32 [G,G,G], info) on count's device.
+    Solid is count / num_views > threshold in float64, as preview_mesh and save_mesh_pkl evaluate it; components.select's rules (keep the
+    `keep` largest components of at least min_voxels voxels; with fill_holes, enclosed cavities become solid).  count_clean is count on
+    kept voxels, 0 on dropped ones and num_views on filled ones, so save_mesh_pkl(path, count_clean, ...) and preview_mesh(count_clean, ...)
+    agree with `data`.  keep=None, min_voxels=1, fill_holes=False changes nothing."""
+    from . import components
+    components._check_selection(keep, min_voxels, connectivity)
+    if int(num_views) < 1:
+        raise ValueError("clean: num_views must be >= 1")
+    if not 0.0 <= float(threshold):
+        raise ValueError("clean: threshold must be >= 0 (a dropped voxel, count 0, has to fail count / num_views > threshold)")
+    if fill_holes and float(threshold) >= 1.0:
+        raise ValueError("clean: fill_holes needs threshold < 1 (a filled voxel, count = num_views, has to pass count / num_views > threshold)")
+    c = count if isinstance(count, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(count))
+    if c.ndim != 3:
+        raise ValueError(f"count must be [X, Y, Z], got {tuple(c.shape)}")
+    if not c.is_cuda:
+        c = c.to(torch.device("cuda", torch.cuda.current_device()))
+    count_clean = c.detach().to(torch.int32).clone().contiguous()
+    solid = (count_clean.to(torch.float64) / num_views > threshold).to(torch.uint8)
+    info = components.clean_grids(solid, [(count_clean, 0, int(num_views))], keep, min_voxels, connectivity, fill_holes)
+    inside = count_clean.to(torch.float64) / num_views > threshold
+    data = torch.where(inside, torch.tensor(float(ior_inside), dtype=torch.float64, device=c.device),
+                       torch.tensor(float(ior_outside), dtype=torch.float64, device=c.device)).to(torch.float32)
+    return data, count_clean, info
+
+
+_clean = clean          # carve's keyword of the same name hides the function
+
+
 def carve(masks, cam_mat, transforms, num_voxels: int, min_point=None, max_point=None, threshold: float = 0.9, device=None,
-          views_per_chunk: Optional[int] = None, return_count: bool = False, ior_inside: float = 1.33, ior_outside: float = 1.0):
+          views_per_chunk: Optional[int] = None, return_count: bool = False, ior_inside: float = 1.33, ior_outside: float = 1.0,
+          clean: Optional[dict] = None):
     """calib/make_visual_hull.py:107-141. -> (data float32 [G,G,G] on `device`, ndim, nmin, nmax[, count int32 [G,G,G]]).
     masks: [V,H,W] uint8 or bool (torch or numpy) or a list of [H,W] arrays, > 0 = object; transforms: V camera-to-world 4x4 matrices;
-    min_point / max_point None: the default box of init_bounding_box.  The views go to the device views_per_chunk at a time."""
+    min_point / max_point None: the default box of init_bounding_box.  The views go to the device views_per_chunk at a time.
+    clean: None, or the keywords of clean() (keep, min_voxels, connectivity, fill_holes) as a dict: data and count are then the cleaned ones."""
     m = _masks_uint8(masks)
     V, H, W = (int(s) for s in m.shape)
     if len(transforms) != V:
@@ -119,6 +156,8 @@ def carve(masks, cam_mat, transforms, num_voxels: int, min_point=None, max_point
                                               current_stream()), "rnerf_visual_hull_count")
         check(lib.rnerf_visual_hull_finalize(ptr(count), C.byref(spec), V, float(threshold), float(ior_inside), float(ior_outside), ptr(out),
                                              current_stream()), "rnerf_visual_hull_finalize")
+        if clean is not None:
+            out, count, _ = _clean(count, V, threshold, ior_inside=ior_inside, ior_outside=ior_outside, **clean)
     ret = (out, [G] * 3, nmin, nmax)
     return ret + (count,) if return_count else ret
 

@@ -143,6 +143,25 @@ def _voxelize_robust(verts, faces, num_voxels, extent, min_point, max_point, num
     return out, [G] * 3, nmin, nmax
 
 
+def clean(data, keep: Optional[int] = 1, min_voxels: int = 1, connectivity: int = 6, fill_holes: bool = False, ior_inside: float = 1.33,
+          ior_outside: float = 1.0):
+    """The voxelised grid of a proxy mesh that still has loose parts, without them (the reference's README: "remove the noisy components in
+    the proxy geometry in Blender"). -> (data float32 [X,Y,Z] on the device, info).  Solid is data > ior_outside (any sub-sample inside);
+    components.select's rules; dropped voxels become ior_outside, filled ones ior_inside, kept ones keep their mean IoR."""
+    from . import components
+    components._check_selection(keep, min_voxels, connectivity)
+    f = data if isinstance(data, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(data))
+    if f.ndim != 3:
+        G = round(f.numel() ** (1.0 / 3.0))
+        f = f.reshape(G, G, G)
+    if not f.is_cuda:
+        f = f.to(torch.device("cuda", torch.cuda.current_device()))
+    out = f.detach().to(torch.float32).clone().contiguous()
+    solid = (out.to(torch.float64) > float(ior_outside)).to(torch.uint8)
+    info = components.clean_grids(solid, [(out, float(ior_outside), float(ior_inside))], keep, min_voxels, connectivity, fill_holes)
+    return out, info
+
+
 def save_mesh_pkl(path: str, data, extent: float = 0.0, min_point=(-1, -1, -1), max_point=(1, 1, 1), num_voxels: Optional[int] = None) -> None:
     """The dict voxelize_mesh.py:109-116 pickles (data float64 [G^3, 1], x slowest)."""
     a = data.detach().cpu().numpy() if isinstance(data, torch.Tensor) else np.asarray(data)
