@@ -18,7 +18,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import check, current_stream, ptr
 
 CONNECTIVITIES = (6, 18, 26)
@@ -46,9 +46,7 @@ def _solid_uint8(solid, device) -> torch.Tensor:
     s = solid if isinstance(solid, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(solid))
     if s.ndim != 3:
         raise ValueError(f"the grid must be [X, Y, Z], got {tuple(s.shape)}")
-    if device is None:
-        device = s.device if s.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    s = s.detach().to(torch.device(device))
+    s = s.detach().to(ops.device_of(s, device=device))
     if s.dtype == torch.bool:
         s = s.to(torch.uint8)
     elif s.dtype != torch.uint8:
@@ -66,15 +64,12 @@ def label(solid, connectivity: int = 6, phase: int = 1, device=None) -> torch.Te
     s = _solid_uint8(solid, device)
     lib = _lib.load()
     dims = _dims(s.shape)
-    ws_bytes = lib.rnerf_components_workspace_bytes(C.byref(dims))
-    if ws_bytes == 0:
-        check(-1, "rnerf_components_workspace_bytes")
+    workspace = ops.workspace("rnerf_components_workspace_bytes", C.byref(dims), device=s.device)
     with torch.cuda.device(s.device):
-        workspace = torch.empty(ws_bytes // 4, dtype=torch.int32, device=s.device)
         labels = torch.empty(tuple(s.shape), dtype=torch.int32, device=s.device)
         check(lib.rnerf_components_label(ptr(s), C.byref(dims), int(phase), int(connectivity), ptr(labels), ptr(workspace), current_stream()),
               "rnerf_components_label")
-        if int(workspace[0].item()) != 0:
+        if int(workspace[:4].view(torch.int32).item()) != 0:          # the error word
             raise _lib.RnerfError("rnerf_components_label: a find / union loop reached its iteration cap")
     return labels
 

@@ -4,6 +4,7 @@
 //
 // One streaming kernel: no LDS beyond the 768-byte colour table, no atomics.
 #include "common.h"
+#include "eval_host.h"
 #include "magma_table.h"
 
 namespace rnerf {
@@ -72,11 +73,6 @@ __global__ __launch_bounds__(ERRMAP_THREADS) void errmap_sheet_kernel(const floa
   } else {
     for (int e = 0; e < n; ++e) out[at + e] = (unsigned char)b[e];
   }
-}
-
-inline bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
 }
 
 }  // namespace

@@ -23,6 +23,7 @@
 // formula after the vertical pass differs.  Its per-channel map goes to the workspace and channel_mean_kernel averages the channels.
 // summary.py's squared-error map (rnerf_errmap_mse) is here too, for the fixed-order mean it shares with the other two.
 #include "common.h"
+#include "eval_host.h"
 
 #include <math.h>
 
@@ -77,6 +78,17 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// The tail of every fixed-order fp64 sum here, for a workgroup of four waves: each wave adds its lanes (the xor butterfly above), lane 0
+// leaves the wave's sum in red[wave], and the result is ((red[0] + red[1]) + red[2]) + red[3], which thread 0 stores.  The order of
+// these additions is the contract: the sums are bit-reproducible.  Every thread of the workgroup must call it.
+__device__ __forceinline__ double block_sum4(double v, double* red) {
+  const int tid = threadIdx.x;
+  v = wave_sum(v);
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 // Stage input rows [r0, r0 + rc) of the tile (both images) into LDS rows of `lin` floats.  Row r's segment starts at flat offset g;
@@ -237,10 +249,8 @@ __global__ __launch_bounds__(SSIM_THREADS) void ssim_tile_kernel(const float* __
     }
   }
   if (partials) {
-    part = wave_sum(part);
-    if (lane == 0) red[wave] = part;
-    __syncthreads();
-    if (tid == 0) partials[b] = ((red[0] + red[1]) + red[2]) + red[3];
+    part = block_sum4(part, red);
+    if (tid == 0) partials[b] = part;
   }
 }
 
@@ -251,10 +261,8 @@ __global__ __launch_bounds__(SSIM_THREADS) void ssim_mean_kernel(const double* _
   const int tid = threadIdx.x;
   double s = 0.0;
   for (int t = tid; t < tiles; t += SSIM_THREADS) s += partials[img * tiles + t];
-  s = wave_sum(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) mean[img] = (float)((((red[0] + red[1]) + red[2]) + red[3]) / count);
+  s = block_sum4(s, red);
+  if (tid == 0) mean[img] = (float)(s / count);
 }
 
 // The channel mean of a per-channel map float[rows][C] -> float[rows] (ssim_map.mean(1), ssim.py:129): the channels added in order in
@@ -277,6 +285,41 @@ int ssim_check(int64_t n, int32_t H, int32_t W, int32_t C, int32_t fs, SsimPlan*
     return RNERF_ERR_UNSUPPORTED;
   }
   RNERF_CHECK_ARG((long long)p->tiles_x * p->tiles_y * n <= 0xffffffffLL / SSIM_THREADS, "rnerf_ssim: too many tiles for one launch");
+  return RNERF_OK;
+}
+
+// The fs taps exp(exponent(i)) / sum, in double, rounded once.  -> the sum: the taps are set only if it is positive and finite.
+template <class Exponent>
+double ssim_taps(int fs, Exponent exponent, SsimFilter* filt) {
+  double w[SSIM_MAX_FS], sum = 0.0;
+  for (int i = 0; i < fs; ++i) {
+    w[i] = exp(exponent(i));
+    sum += w[i];
+  }
+  *filt = {};
+  if (sum > 0.0 && isfinite(sum))
+    for (int i = 0; i < fs; ++i) filt->w[i] = (float)(w[i] / sum);
+  return sum;
+}
+
+// The tile launch of rnerf_ssim (map: [n][Ho][Wo][C]) and, with SUMMARY, of rnerf_ssim_summary (map: its per-channel map); either of map
+// and partials (one double per tile) may be null.
+template <bool SUMMARY>
+int ssim_launch(const SsimPlan& p, const SsimFilter& filt, float c1, float c2, const float* img0, const float* img1, int64_t n, int H, int W,
+                int C, int fs, float* map, double* partials, hipStream_t st) {
+  const long long total = n * H * (long long)W * C;
+  const int vec = ((((uintptr_t)img0) | ((uintptr_t)img1)) & 15) == 0;
+  const dim3 grid((unsigned)((long long)p.tiles_x * p.tiles_y * n)), block(SSIM_THREADS);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, block, p.lds, st, img0, img1, H, W, C, fs, p.rc, p.lin, p.tiles_x, p.tiles_y, filt, c1, c2, total, vec, map,
+                       partials);
+  };
+  switch (p.rpt) {
+    case 4: launch(ssim_tile_kernel<4, SUMMARY>); break;
+    case 2: launch(ssim_tile_kernel<2, SUMMARY>); break;
+    default: launch(ssim_tile_kernel<1, SUMMARY>); break;
+  }
+  RNERF_CHECK_LAUNCH();
   return RNERF_OK;
 }
 
@@ -306,16 +349,9 @@ __global__ __launch_bounds__(SSIM_THREADS) void errmap_mse_kernel(const float* _
     if (map) map[img * hw + px] = fdiv(sum, (float)C);
   }
   if (partials) {
-    part = wave_sum(part);
-    if ((tid & 63) == 0) red[tid >> 6] = part;
-    __syncthreads();
-    if (tid == 0) partials[blk] = ((red[0] + red[1]) + red[2]) + red[3];
+    part = block_sum4(part, red);
+    if (tid == 0) partials[blk] = part;
   }
-}
-
-inline bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
 }
 
 int errmap_mse_check(int64_t n, int32_t H, int32_t W, int32_t C, long long* blocks_per_image) {
@@ -552,10 +588,8 @@ __global__ __launch_bounds__(FLIP_THREADS) void flip_vertical_kernel(const float
     }
   }
   if (partials) {
-    part = wave_sum(part);
-    if (lane == 0) red[wave] = part;
-    __syncthreads();
-    if (tid == 0) partials[blk] = ((red[0] + red[1]) + red[2]) + red[3];
+    part = block_sum4(part, red);
+    if (tid == 0) partials[blk] = part;
   }
 }
 
@@ -660,32 +694,15 @@ extern "C" int rnerf_ssim(const float* img0, const float* img1, int64_t n, int32
   // rnerf/utils.py:435-439, in double, rounded once
   const int fs = filter_size, hw = fs / 2;
   const double shift = (2 * hw - fs + 1) / 2.0;
-  double w[SSIM_MAX_FS], sum = 0.0;
-  for (int i = 0; i < fs; ++i) {
-    const double t = (i - hw + shift) / filter_sigma;
-    w[i] = exp(-0.5 * t * t);
-    sum += w[i];
-  }
+  SsimFilter filt;
+  const double sum = ssim_taps(fs, [&](int i) { const double t = (i - hw + shift) / filter_sigma; return -0.5 * t * t; }, &filt);
   RNERF_CHECK_ARG(sum > 0.0 && isfinite(sum), "rnerf_ssim: the filter's weights sum to %g", sum);
-  SsimFilter filt = {};
-  for (int i = 0; i < fs; ++i) filt.w[i] = (float)(w[i] / sum);
   const float c1 = (float)((k1 * max_val) * (k1 * max_val)), c2 = (float)((k2 * max_val) * (k2 * max_val));
-  const long long total = n * H * (long long)W * C;
-  const int vec = ((((uintptr_t)img0) | ((uintptr_t)img1)) & 15) == 0;
   const long long tiles = (long long)p.tiles_x * p.tiles_y;
   hipStream_t st = (hipStream_t)stream;
   double* partials = mean ? (double*)workspace : nullptr;
-  const dim3 grid((unsigned)(tiles * n)), block(SSIM_THREADS);
-#define RNERF_SSIM_LAUNCH(R)                                                                                                              \
-  hipLaunchKernelGGL((ssim_tile_kernel<R, false>), grid, block, p.lds, st, img0, img1, H, W, C, fs, p.rc, p.lin, p.tiles_x, p.tiles_y, filt, c1, c2, \
-                     total, vec, map, partials)
-  switch (p.rpt) {
-    case 4: RNERF_SSIM_LAUNCH(4); break;
-    case 2: RNERF_SSIM_LAUNCH(2); break;
-    default: RNERF_SSIM_LAUNCH(1); break;
-  }
-#undef RNERF_SSIM_LAUNCH
-  RNERF_CHECK_LAUNCH();
+  const int launched = ssim_launch<false>(p, filt, c1, c2, img0, img1, n, H, W, C, fs, map, partials, st);
+  if (launched != RNERF_OK) return launched;
   if (mean) {
     const double count = (double)(H - fs + 1) * (double)(W - fs + 1) * (double)C;
     hipLaunchKernelGGL(ssim_mean_kernel, dim3((unsigned)n), dim3(SSIM_THREADS), 0, st, partials, (int)tiles, count, mean);
@@ -745,33 +762,16 @@ extern "C" int rnerf_ssim_summary(const float* img0, const float* img1, int64_t 
   RNERF_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "rnerf_ssim_summary: the workspace must be 8-byte aligned");
   // _fspecial_gauss_1d (ssim.py:20-24), in double, rounded once
   const int fs = filter_size;
-  double w[SSIM_MAX_FS], sum = 0.0;
-  for (int i = 0; i < fs; ++i) {
-    const double t = (double)(i - fs / 2);
-    w[i] = exp(-(t * t) / (2.0 * filter_sigma * filter_sigma));
-    sum += w[i];
-  }
+  SsimFilter filt;
+  const double sum = ssim_taps(fs, [&](int i) { const double t = (double)(i - fs / 2); return -(t * t) / (2.0 * filter_sigma * filter_sigma); }, &filt);
   RNERF_CHECK_ARG(sum > 0.0 && isfinite(sum), "rnerf_ssim_summary: the filter's weights sum to %g", sum);
-  SsimFilter filt = {};
-  for (int i = 0; i < fs; ++i) filt.w[i] = (float)(w[i] / sum);
   const float c1 = (float)((0.01 * data_range) * (0.01 * data_range)), c2 = (float)((0.03 * data_range) * (0.03 * data_range));
-  const long long total = n * H * (long long)W * C;
-  const int vec = ((((uintptr_t)img0) | ((uintptr_t)img1)) & 15) == 0;
   const long long tiles = (long long)p.tiles_x * p.tiles_y;
   hipStream_t st = (hipStream_t)stream;
   double* partials = mean ? (double*)workspace : nullptr;
   float* per_channel = map ? (float*)((char*)workspace + ssim_summary_partials_bytes(n, p)) : nullptr;
-  const dim3 grid((unsigned)(tiles * n)), block(SSIM_THREADS);
-#define RNERF_SSIM_LAUNCH(R)                                                                                                                    \
-  hipLaunchKernelGGL((ssim_tile_kernel<R, true>), grid, block, p.lds, st, img0, img1, H, W, C, fs, p.rc, p.lin, p.tiles_x, p.tiles_y, filt, c1, \
-                     c2, total, vec, per_channel, partials)
-  switch (p.rpt) {
-    case 4: RNERF_SSIM_LAUNCH(4); break;
-    case 2: RNERF_SSIM_LAUNCH(2); break;
-    default: RNERF_SSIM_LAUNCH(1); break;
-  }
-#undef RNERF_SSIM_LAUNCH
-  RNERF_CHECK_LAUNCH();
+  const int launched = ssim_launch<true>(p, filt, c1, c2, img0, img1, n, H, W, C, fs, per_channel, partials, st);
+  if (launched != RNERF_OK) return launched;
   const long long pixels = n * (long long)(H - fs + 1) * (W - fs + 1);
   if (map) {
     hipLaunchKernelGGL(channel_mean_kernel, dim3((unsigned)((pixels + SSIM_THREADS - 1) / SSIM_THREADS)), dim3(SSIM_THREADS), 0, st, per_channel, pixels, C, map);

@@ -7,6 +7,7 @@
 // than RASTER_SMALL tiles goes to one list every tile walks instead (the workspace is then bounded by the mesh, not by the view).  The
 // atomics decide the ORDER of a list only; depth is a minimum, tri a minimum among equals and hits a count, so no output sees that order.
 #include "common.h"
+#include "eval_host.h"
 
 #include <math.h>
 
@@ -238,8 +239,6 @@ __global__ void __launch_bounds__(256) dilate_rect_kernel(const RectAcc* __restr
     bbox[0] = any ? all.x0 : 0; bbox[1] = any ? all.y0 : 0; bbox[2] = any ? all.x1 - all.x0 + 1 : 0; bbox[3] = any ? all.y1 - all.y0 + 1 : 0;
   }
 }
-
-static inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 static bool raster_shape(int64_t V, int64_t F, int32_t H, int32_t W) {
   return V >= 0 && V < (1LL << 31) && F >= 0 && F < (1LL << 29) && H >= 1 && W >= 1 && (int64_t)H * W < (1LL << 31);

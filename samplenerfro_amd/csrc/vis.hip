@@ -5,6 +5,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "eval_host.h"
 #include "turbo_table.h"
 
 namespace rnerf {
@@ -401,7 +402,6 @@ __global__ __launch_bounds__(VIS_THREADS) void vis_normals_map_kernel(const floa
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-inline size_t al16(size_t n) { return (n + 15) & ~(size_t)15; }
 inline int reduce_blocks(long long N) { const long long b = (N + VIS_THREADS - 1) / VIS_THREADS; return (int)(b < VIS_MAX_PARTIALS ? b : VIS_MAX_PARTIALS); }
 
 struct SortPlan { long long tile; int nb; };
@@ -419,14 +419,14 @@ struct DepthLayout { size_t ranges, keys, idx, hist, cum, sel, total; };
 inline DepthLayout depth_layout(long long N, bool sort) {
   DepthLayout l = {};
   size_t at = 0;
-  l.ranges = at; at += al16(sizeof(VisRange) * VIS_MAX_PARTIALS);
+  l.ranges = at; at += up16(sizeof(VisRange) * VIS_MAX_PARTIALS);
   if (sort) {
     const SortPlan p = sort_plan(N);
-    l.keys = at; at += 2 * al16(sizeof(unsigned) * (size_t)N);
-    l.idx = at; at += 2 * al16(sizeof(unsigned) * (size_t)N);
-    l.hist = at; at += al16(sizeof(unsigned) * 256 * (size_t)p.nb);
-    l.cum = at; at += al16(sizeof(double) * (size_t)p.nb);
-    l.sel = at; at += al16(sizeof(unsigned) * 2 * (size_t)p.nb);
+    l.keys = at; at += 2 * up16(sizeof(unsigned) * (size_t)N);
+    l.idx = at; at += 2 * up16(sizeof(unsigned) * (size_t)N);
+    l.hist = at; at += up16(sizeof(unsigned) * 256 * (size_t)p.nb);
+    l.cum = at; at += up16(sizeof(double) * (size_t)p.nb);
+    l.sel = at; at += up16(sizeof(unsigned) * 2 * (size_t)p.nb);
   }
   l.total = at;
   return l;
@@ -441,12 +441,6 @@ int vis_check_size(const char* who, int32_t H, int32_t W) {
 int vis_check_frac(double ignore_frac) {
   RNERF_CHECK_ARG(isfinite(ignore_frac) && ignore_frac >= 0.0 && ignore_frac < 0.5, "rnerf_vis_depth: ignore_frac must be in [0, 0.5)");
   return RNERF_OK;
-}
-
-inline bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-  if (!a || !b) return false;
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + nb && pb < pa + na;
 }
 
 }  // namespace
@@ -491,7 +485,7 @@ extern "C" int rnerf_vis_depth(const float* depth, const float* acc, int32_t H, 
     RNERF_CHECK_LAUNCH();
   } else if (sort) {
     const SortPlan p = sort_plan(N);
-    const size_t stride = al16(sizeof(unsigned) * (size_t)N);
+    const size_t stride = up16(sizeof(unsigned) * (size_t)N);
     unsigned* keys[2] = {(unsigned*)(ws + l.keys), (unsigned*)(ws + l.keys + stride)};
     unsigned* idx[2] = {(unsigned*)(ws + l.idx), (unsigned*)(ws + l.idx + stride)};
     unsigned* hist = (unsigned*)(ws + l.hist);
@@ -523,7 +517,7 @@ extern "C" int rnerf_vis_depth(const float* depth, const float* acc, int32_t H, 
 
 extern "C" size_t rnerf_vis_normals_workspace_bytes(int32_t H, int32_t W) {
   if (vis_check_size("rnerf_vis_normals", H, W) != RNERF_OK) return 0;
-  return 2 * al16(sizeof(VisMoments) * VIS_MAX_PARTIALS);
+  return 2 * up16(sizeof(VisMoments) * VIS_MAX_PARTIALS);
 }
 
 extern "C" int rnerf_vis_normals(const float* depth, const float* acc, int32_t H, int32_t W, double scaling, float* rgb, float* normals,
@@ -544,7 +538,7 @@ extern "C" int rnerf_vis_normals(const float* depth, const float* acc, int32_t H
   int num_partials = 0;
   if (need_auto) {
     VisMoments* first = (VisMoments*)workspace;
-    second = (VisMoments*)((char*)workspace + al16(sizeof(VisMoments) * VIS_MAX_PARTIALS));
+    second = (VisMoments*)((char*)workspace + up16(sizeof(VisMoments) * VIS_MAX_PARTIALS));
     num_partials = reduce_blocks(N);
     hipLaunchKernelGGL(vis_moments1_kernel, dim3(num_partials), dim3(VIS_THREADS), 0, st, depth, N, (int)W, first);
     RNERF_CHECK_LAUNCH();

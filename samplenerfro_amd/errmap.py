@@ -22,27 +22,14 @@ MAP_NAMES = ("psnr", "ssim", "flip")      # summary.py:232 without "lpips"
 MAP_NAMES_LPIPS = ("psnr", "ssim", "lpips", "flip")      # summary.py:232
 
 
-def _device_of(*xs) -> torch.device:
-    for x in xs:
-        if isinstance(x, torch.Tensor) and x.is_cuda:
-            return x.device
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _as_f32(t, dev: torch.device) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float32)))
-    return t.to(device=dev, dtype=torch.float32)
-
-
 _q8_tables: dict = {}                     # device -> float32 [256]: i / 255 as the reader of a PNG forms it
 
 
 def quantize8(img):
     """What a reader of utils.save_img's PNG gets back (summary.py:30-38 after rnerf/utils.py:474-488): trunc(clip(x, 0, 1) * 255) / 255 in
     float32, on the device.  summary.py scores the PNG on disk, not the float render.  NaN gives 0."""
-    dev = _device_of(img)
-    x = _as_f32(img, dev)
+    dev = ops.device_of(img)
+    x = ops.as_f32(img, dev)
     table = _q8_tables.get(dev)
     if table is None:
         table = _q8_tables[dev] = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255.0)).to(dev)
@@ -60,8 +47,8 @@ def error_maps(reference, test, pixels_per_degree=utils.FLIP_PPD_SUMMARY, lpips=
         raise ValueError(f"error_maps: need two [H, W, 3] images, got shapes {s0} and {s1}")
     if s0[0] < 11 or s0[1] < 11:
         raise ValueError(f"error_maps: the images ({s0[0]} x {s0[1]}) are smaller than the 11 x 11 SSIM window")
-    dev = _device_of(reference, test)
-    a, b = _as_f32(reference, dev), _as_f32(test, dev)
+    dev = ops.device_of(reference, test)
+    a, b = ops.as_f32(reference, dev), ops.as_f32(test, dev)
     mse_map, mse = ops.errmap_mse(a, b)
     ssim_map, ssim = ops.ssim_summary(a, b, data_range=1.0)
     flip_map, flip = ops.flip(a, b, pixels_per_degree=float(pixels_per_degree), return_both=True)
@@ -78,14 +65,14 @@ def error_maps(reference, test, pixels_per_degree=utils.FLIP_PPD_SUMMARY, lpips=
 def sheet(reference, test, maps) -> torch.Tensor:
     """summary.py:231-240 -> uint8 [H, (2 + K)(W + 5), 3] on the device: reference | test | the K <= 4 maps ([h_k, w_k], h_k <= H,
     w_k <= W) through the magma colours, each in the top-left corner of a black H x W panel; 5 white columns after every panel."""
-    dev = _device_of(reference, test, *maps)
-    return ops.errmap_sheet(_as_f32(reference, dev), _as_f32(test, dev), [_as_f32(m, dev) for m in maps])
+    dev = ops.device_of(reference, test, *maps)
+    return ops.errmap_sheet(ops.as_f32(reference, dev), ops.as_f32(test, dev), [ops.as_f32(m, dev) for m in maps])
 
 
 def colorize(error_map) -> torch.Tensor:
     """save_err (summary.py:43-45) -> uint8 [h, w, 3] on the device: the panel of a one-map sheet."""
-    dev = _device_of(error_map)
-    m = _as_f32(error_map, dev)
+    dev = ops.device_of(error_map)
+    m = ops.as_f32(error_map, dev)
     if m.dim() != 2:
         raise ValueError(f"colorize: need a [h, w] map, got shape {tuple(m.shape)}")
     h, w = int(m.shape[0]), int(m.shape[1])

@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import check, current_stream, ptr
 
 
@@ -26,16 +26,11 @@ def marching_cubes(field, iso: float, device=None):
     f = field if isinstance(field, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(field))
     if f.ndim != 3:
         raise ValueError(f"field must be [Gx, Gy, Gz], got {tuple(f.shape)}")
-    if device is None:
-        device = f.device if f.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
+    device = ops.device_of(f, device=device)
     f = f.detach().to(device=device, dtype=torch.float32).contiguous()
     dims = (C.c_int32 * 3)(*[int(s) for s in f.shape])
-    ws_bytes = lib.rnerf_marching_cubes_workspace_bytes(C.byref(dims))
-    if ws_bytes == 0:
-        check(-1, "rnerf_marching_cubes_workspace_bytes")
+    workspace = ops.workspace("rnerf_marching_cubes_workspace_bytes", C.byref(dims), device=device)
     with torch.cuda.device(device):
-        workspace = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=device)
         totals = torch.empty(2, dtype=torch.int64, device=device)
         check(lib.rnerf_marching_cubes_count(ptr(f), C.byref(dims), float(iso), ptr(workspace), ptr(totals), current_stream()),
               "rnerf_marching_cubes_count")

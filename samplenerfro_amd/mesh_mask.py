@@ -23,22 +23,13 @@ from typing import Iterable, Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import RnerfError, check, current_stream, ptr
-
-
-def _device(device, *tensors):
-    if device is not None:
-        return torch.device(device)
-    for t in tensors:
-        if isinstance(t, torch.Tensor) and t.is_cuda:
-            return t.device
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def upload_mesh(verts, faces, device=None):
     """-> (verts float64 [V, 3], faces int32 [F, 3]) contiguous on the device; the face indices are checked here (the kernels trust them)."""
-    device = _device(device, verts, faces)
+    device = ops.device_of(verts, faces, device=device)
     v = verts if isinstance(verts, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(verts, np.float64)))
     f = faces if isinstance(faces, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(faces).astype(np.int32, copy=False)))
     v = v.detach().to(device=device, dtype=torch.float64).reshape(-1, 3).contiguous()
@@ -54,10 +45,7 @@ def _camera(H: int, W: int, focal, cam_mat, pixel_center: bool):
     """The camera arguments of ops.generate_rays: Blender model with `focal`, OpenCV model with `cam_mat`."""
     if (focal is None) == (cam_mat is None):
         raise ValueError("give focal (Blender model) or cam_mat (OpenCV model)")
-    pc = 0.5 if pixel_center else 0.0
-    if cam_mat is None:
-        return (0, float(focal), float(focal), W * 0.5, H * 0.5, pc)
-    return (1, float(cam_mat[0][0]), float(cam_mat[1][1]), float(cam_mat[0][2]), float(cam_mat[1][2]), pc)
+    return ops.camera_args(H, W, focal, cam_mat) + (0.5 if pixel_center else 0.0,)
 
 
 def _render_uploaded(v, f, camtoworld, H, W, cam, znear, zfar, want_tri, want_hits, allow_skipped, workspace=None):
@@ -69,10 +57,7 @@ def _render_uploaded(v, f, camtoworld, H, W, cam, znear, zfar, want_tri, want_hi
     V, F = int(v.shape[0]), int(f.shape[0])
     with torch.cuda.device(dev):
         if workspace is None:
-            ws_bytes = lib.rnerf_mesh_depth_workspace_bytes(V, F, int(H), int(W))
-            if ws_bytes == 0:
-                check(-1, "rnerf_mesh_depth_workspace_bytes")
-            workspace = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+            workspace = ops.workspace("rnerf_mesh_depth_workspace_bytes", V, F, int(H), int(W), device=dev)
         depth = torch.empty((H, W), dtype=torch.float32, device=dev)
         tri = torch.empty((H, W), dtype=torch.int32, device=dev) if want_tri else None
         hits = torch.empty((H, W), dtype=torch.int32, device=dev) if want_hits else None
@@ -109,11 +94,8 @@ def _dilate(mask: torch.Tensor, ky: int, kx: int, want_bbox: bool):
         raise ValueError("mask must be a uint8 [H, W] device tensor")
     m = mask.contiguous()
     H, W = int(m.shape[0]), int(m.shape[1])
-    ws_bytes = lib.rnerf_mask_dilate_workspace_bytes(H, W)
-    if ws_bytes == 0:
-        check(-1, "rnerf_mask_dilate_workspace_bytes")
+    workspace = ops.workspace("rnerf_mask_dilate_workspace_bytes", H, W, device=m.device)
     with torch.cuda.device(m.device):
-        workspace = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=m.device)
         out = torch.empty_like(m)
         bbox = torch.empty(4, dtype=torch.int32, device=m.device) if want_bbox else None
         check(lib.rnerf_mask_dilate(ptr(m), H, W, int(ky), int(kx), ptr(out), ptr(bbox), ptr(workspace), current_stream()), "rnerf_mask_dilate")
@@ -127,7 +109,7 @@ def _as_mask(mask, device=None) -> torch.Tensor:
         m = m[..., 0]
     if m.ndim != 2:
         raise ValueError(f"a mask must be [H, W], got {tuple(m.shape)}")
-    return (m.to(_device(device, m)) > 0).to(torch.uint8)
+    return (m.to(ops.device_of(m, device=device)) > 0).to(torch.uint8)
 
 
 def dilate(mask, size=35) -> torch.Tensor:
@@ -149,11 +131,7 @@ def render_masks(verts, faces, camtoworlds: Iterable, H: int, W: int, *, dilate:
     once and the workspace is shared.  dilate: the box size (35 there; 0 or 1: the bare silhouette)."""
     v, f = upload_mesh(verts, faces, device)
     cam = _camera(H, W, focal, cam_mat, pixel_center)
-    lib = _lib.load()
-    ws_bytes = lib.rnerf_mesh_depth_workspace_bytes(int(v.shape[0]), int(f.shape[0]), int(H), int(W))
-    if ws_bytes == 0:
-        check(-1, "rnerf_mesh_depth_workspace_bytes")
-    workspace = torch.empty(ws_bytes // 8, dtype=torch.int64, device=v.device)
+    workspace = ops.workspace("rnerf_mesh_depth_workspace_bytes", int(v.shape[0]), int(f.shape[0]), int(H), int(W), device=v.device)
     for c2w in camtoworlds:
         depth, _, _, _ = _render_uploaded(v, f, c2w, int(H), int(W), cam, znear, zfar, False, False, allow_skipped, workspace)
         mask = (depth != 0).to(torch.uint8)                                   # render_mask.py:91

@@ -24,6 +24,51 @@ def _chk(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+_workspaces: dict = {}            # (query name, device index, stream) -> uint8 tensor: the workspaces of workspace(..., keep_for=stream)
+
+
+def workspace(name: str, *args, device, keep_for: Optional[int] = None) -> torch.Tensor:
+    """A uint8 tensor on `device` of at least the bytes `lib.<name>(*args)` answers (an rnerf_*_workspace_bytes query; 0 is its error).
+    keep_for: a stream handle — the buffer is kept for that device and stream and grown when a later call needs more."""
+    nb = getattr(_lib.load(), name)(*args)
+    if nb == 0:
+        check(-1, name)
+    if keep_for is None:
+        return torch.empty(nb, dtype=torch.uint8, device=device)
+    key = (name, torch.device(device).index, keep_for)
+    ws = _workspaces.get(key)
+    if ws is None or ws.numel() < nb:
+        ws = _workspaces[key] = torch.empty(nb, dtype=torch.uint8, device=device)
+    return ws
+
+
+def device_of(*xs, device=None) -> torch.device:
+    """`device` if given, else the device of the first CUDA tensor among xs, else the current CUDA device."""
+    if device is not None:
+        return torch.device(device)
+    for x in xs:
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            return x.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def as_f32(t, dev: torch.device):
+    """A tensor, numpy array or array-like (None stays None) as a float32 tensor on dev."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor):
+        import numpy as np
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float32)))
+    return t.to(device=dev, dtype=torch.float32)
+
+
+def camera_args(H: int, W: int, focal, cam_mat):
+    """(model, fx, fy, cx, cy) of rnerf_generate_rays: Blender model with `focal`, OpenCV model with `cam_mat`."""
+    if cam_mat is None:
+        return (0, float(focal), float(focal), W * 0.5, H * 0.5)
+    return (1, float(cam_mat[0][0]), float(cam_mat[1][1]), float(cam_mat[0][2]), float(cam_mat[1][2]))
+
+
 def grid_prefilter(grid: torch.Tensor, ksize: int, ksigma: float) -> torch.Tensor:
     """G1: ior_utils.conv3d_normal (rnerf/ior_utils.py:327-363). grid [Gx,Gy,Gz] f32 -> same shape."""
     lib = _lib.load()
@@ -290,7 +335,6 @@ def bkgd_backward(params_flat: torch.Tensor, save: torch.Tensor, d_out: torch.Te
 
 def stratified_u(key, B: int, num_fine: int, device) -> torch.Tensor:
     """S1 randomized draws on the device (rnerf/model_utils.py:345-354) -> u [num_fine, B]."""
-    import ctypes as C
     lib = _lib.load()
     k = (C.c_uint32 * 2)(int(key[0]), int(key[1]))
     u = torch.empty((num_fine, B), dtype=torch.float32, device=device)
@@ -311,11 +355,7 @@ def generate_rays(camtoworld, H: int, W: int, device, focal: Optional[float] = N
     v = torch.empty_like(o)
     d = torch.empty_like(o) if want_directions else None
     pc = 0.5 if pixel_center else 0.0
-    if cam_mat is None:
-        args = (0, float(focal), float(focal), W * 0.5, H * 0.5)
-    else:
-        args = (1, float(cam_mat[0][0]), float(cam_mat[1][1]), float(cam_mat[0][2]), float(cam_mat[1][2]))
-    check(lib.rnerf_generate_rays(c2w.ctypes.data_as(C.c_void_p), args[0], args[1], args[2], args[3], args[4], pc, int(W), int(r0), int(n),
+    check(lib.rnerf_generate_rays(c2w.ctypes.data_as(C.c_void_p), *camera_args(H, W, focal, cam_mat), pc, int(W), int(r0), int(n),
                                   ptr(o), ptr(d), ptr(v), current_stream()), "rnerf_generate_rays")
     return o, d, v
 
@@ -622,46 +662,45 @@ def integrated_pos_enc(rows_pd: torch.Tensor, rows_dr: torch.Tensor, node_of_sam
     return (enc, mean, cov) if want_gaussians else enc
 
 
+def _image_pair(a: torch.Tensor, b: torch.Tensor, what: str, names=("reference", "test"), channels: Optional[int] = None):
+    """The checks every two-image entry point makes -> (a, b, lead, n, H, W, Ch) for [*lead, H, W, Ch] images, n the product of lead."""
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"{what}: the images differ in shape: {tuple(a.shape)} vs {tuple(b.shape)}")
+    if a.dim() < 3 or (channels is not None and int(a.shape[-1]) != channels):
+        raise ValueError(f"{what}: need [..., H, W, {channels or 'C'}] images, got shape {tuple(a.shape)}")
+    if a.device != b.device:
+        raise ValueError(f"{what}: the images are on different devices ({a.device}, {b.device})")
+    *lead, H, W, Ch = (int(s) for s in a.shape)
+    n = 1
+    for s in lead:
+        n *= s
+    return _chk(a, names[0]), _chk(b, names[1]), tuple(lead), n, H, W, Ch
+
+
 def ssim(img0: torch.Tensor, img1: torch.Tensor, *, max_val: float, filter_size: int = 11, filter_sigma: float = 1.5, k1: float = 0.01,
          k2: float = 0.03, return_map: bool = False) -> torch.Tensor:
     """compute_ssim (rnerf/utils.py:404-471) on the device (rnerf_ssim).  img0, img1: float32 device tensors [..., H, W, C].
     -> the mean SSIM of each image, shape [...] (0-dim for [H, W, C]), or with return_map the map [..., H-fs+1, W-fs+1, C].
     Issued on the current stream of the images' device; nothing is synchronised."""
-    if tuple(img0.shape) != tuple(img1.shape):
-        raise ValueError(f"ssim: the images differ in shape: {tuple(img0.shape)} vs {tuple(img1.shape)}")
-    if img0.dim() < 3:
-        raise ValueError(f"ssim: need [..., H, W, C] images, got shape {tuple(img0.shape)}")
+    a, b, lead, n, H, W, Ch = _image_pair(img0, img1, "ssim", ("img0", "img1"))
     fs = int(filter_size)
-    *lead, H, W, Ch = (int(s) for s in img0.shape)
     if not 1 <= fs <= 31:
         raise ValueError(f"ssim: filter_size must be in [1, 31], got {fs}")
     if H < fs or W < fs:
         raise ValueError(f"ssim: the images ({H} x {W}) are smaller than the window (filter_size {fs})")
-    if img0.device != img1.device:
-        raise ValueError(f"ssim: the images are on different devices ({img0.device}, {img1.device})")
-    a, b = _chk(img0, "img0"), _chk(img1, "img1")
-    n = 1
-    for s in lead:
-        n *= s
     dev = a.device
     if n == 0 or Ch == 0:
-        return torch.empty(tuple(lead) + ((H - fs + 1, W - fs + 1, Ch) if return_map else ()), dtype=torch.float32, device=dev)
+        return torch.empty(lead + ((H - fs + 1, W - fs + 1, Ch) if return_map else ()), dtype=torch.float32, device=dev)
     lib = _lib.load()
     with torch.cuda.device(dev):
-        out_map = torch.empty(tuple(lead) + (H - fs + 1, W - fs + 1, Ch), dtype=torch.float32, device=dev) if return_map else None
+        out_map = torch.empty(lead + (H - fs + 1, W - fs + 1, Ch), dtype=torch.float32, device=dev) if return_map else None
         mean, ws = None, None
         if not return_map:
-            mean = torch.empty(tuple(lead), dtype=torch.float32, device=dev)
-            nb = lib.rnerf_ssim_workspace_bytes(n, H, W, Ch, fs)
-            if nb == 0:
-                check(-1, "rnerf_ssim_workspace_bytes")
-            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            mean = torch.empty(lead, dtype=torch.float32, device=dev)
+            ws = workspace("rnerf_ssim_workspace_bytes", n, H, W, Ch, fs, device=dev)
         check(lib.rnerf_ssim(ptr(a), ptr(b), n, H, W, Ch, fs, float(filter_sigma), float(max_val), float(k1), float(k2), ptr(out_map),
                              ptr(mean), ptr(ws), torch.cuda.current_stream(dev).cuda_stream), "rnerf_ssim")
     return out_map if return_map else mean
-
-
-_flip_workspaces: dict = {}       # (device index, stream) -> uint8 tensor: rnerf_flip's workspace, kept and grown between calls
 
 
 def flip(reference: torch.Tensor, test: torch.Tensor, *, pixels_per_degree: float, return_map: bool = False, return_both: bool = False):
@@ -669,34 +708,18 @@ def flip(reference: torch.Tensor, test: torch.Tensor, *, pixels_per_degree: floa
     [..., H, W, 3], sRGB in [0, 1].  -> the mean FLIP error of each image, shape [...] (0-dim for [H, W, 3]), or with return_map the
     error map [..., H, W].  Issued on the current stream of the images' device; nothing is synchronised.  The workspace (14 filtered
     planes) is kept per device and stream and reused by later calls that fit in it.  return_both: -> (map, mean) from the one call."""
-    if tuple(reference.shape) != tuple(test.shape):
-        raise ValueError(f"flip: the images differ in shape: {tuple(reference.shape)} vs {tuple(test.shape)}")
-    if reference.dim() < 3 or int(reference.shape[-1]) != 3:
-        raise ValueError(f"flip: need [..., H, W, 3] images, got shape {tuple(reference.shape)}")
-    if reference.device != test.device:
-        raise ValueError(f"flip: the images are on different devices ({reference.device}, {test.device})")
+    a, b, lead, n, H, W, _ = _image_pair(reference, test, "flip", channels=3)
     ppd = float(pixels_per_degree)
-    *lead, H, W, _ = (int(s) for s in reference.shape)
-    a, b = _chk(reference, "reference"), _chk(test, "test")
-    n = 1
-    for s in lead:
-        n *= s
     dev = a.device
     if n == 0 or H == 0 or W == 0:
-        empty = lambda shape: torch.empty(tuple(lead) + shape, dtype=torch.float32, device=dev)
+        empty = lambda shape: torch.empty(lead + shape, dtype=torch.float32, device=dev)
         return (empty((H, W)), empty(())) if return_both else empty((H, W) if return_map else ())
     lib = _lib.load()
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        nb = lib.rnerf_flip_workspace_bytes(n, H, W, ppd)
-        if nb == 0:
-            check(-1, "rnerf_flip_workspace_bytes")
-        key = (dev.index, stream)
-        ws = _flip_workspaces.get(key)
-        if ws is None or ws.numel() < nb:
-            ws = _flip_workspaces[key] = torch.empty(nb, dtype=torch.uint8, device=dev)
-        out_map = torch.empty(tuple(lead) + (H, W), dtype=torch.float32, device=dev) if return_map or return_both else None
-        mean = None if return_map and not return_both else torch.empty(tuple(lead), dtype=torch.float32, device=dev)
+        ws = workspace("rnerf_flip_workspace_bytes", n, H, W, ppd, device=dev, keep_for=stream)
+        out_map = torch.empty(lead + (H, W), dtype=torch.float32, device=dev) if return_map or return_both else None
+        mean = None if return_map and not return_both else torch.empty(lead, dtype=torch.float32, device=dev)
         check(lib.rnerf_flip(ptr(a), ptr(b), n, H, W, ppd, ptr(out_map), ptr(mean), ptr(ws), stream), "rnerf_flip")
     if return_both:
         return out_map, mean
@@ -704,7 +727,6 @@ def flip(reference: torch.Tensor, test: torch.Tensor, *, pixels_per_degree: floa
 
 
 LPIPS_MIN_SIZE = 31               # below it AlexNet's second pool is empty
-_lpips_workspaces: dict = {}      # (device index, stream) -> uint8 tensor: rnerf_lpips' workspace, kept and grown between calls
 
 
 def lpips_layer_shapes(H: int, W: int):
@@ -722,40 +744,24 @@ def lpips(a: torch.Tensor, b: torch.Tensor, weights, return_both: bool = False, 
     unclipped map [..., H, W]; with return_both (map, value) from the one call.  return_layers appends the five d_l as a list of
     [..., h_l, w_l] views.  Issued on the current stream of the images' device; nothing is synchronised.  The workspace is kept per
     device and stream and reused by later calls that fit in it."""
-    if tuple(a.shape) != tuple(b.shape):
-        raise ValueError(f"lpips: the images differ in shape: {tuple(a.shape)} vs {tuple(b.shape)}")
-    if a.dim() < 3 or int(a.shape[-1]) != 3:
-        raise ValueError(f"lpips: need [..., H, W, 3] images, got shape {tuple(a.shape)}")
-    if a.device != b.device:
-        raise ValueError(f"lpips: the images are on different devices ({a.device}, {b.device})")
-    *lead, H, W, _ = (int(s) for s in a.shape)
+    x, y, lead, n, H, W, _ = _image_pair(a, b, "lpips", ("a", "b"), channels=3)
     if H < LPIPS_MIN_SIZE or W < LPIPS_MIN_SIZE:
         raise ValueError(f"lpips: LPIPS needs images of at least {LPIPS_MIN_SIZE} x {LPIPS_MIN_SIZE}, got {H} x {W}")
-    flat = getattr(weights, "flat", weights)
-    x, y, wt = _chk(a, "a"), _chk(b, "b"), _chk(flat, "weights")
+    wt = _chk(getattr(weights, "flat", weights), "weights")
     if wt.numel() != _lib.LPIPS_WEIGHT_FLOATS:
         raise _lib.RnerfError(f"lpips: the weights hold {wt.numel()} floats, not {_lib.LPIPS_WEIGHT_FLOATS}")
     dev = x.device
     if wt.device != dev:
         raise ValueError(f"lpips: the weights are on {wt.device}, the images on {dev}")
-    n = 1
-    for s in lead:
-        n *= s
     if n == 0:
         raise ValueError(f"lpips: empty batch, shape {tuple(a.shape)}")
     lib = _lib.load()
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        nb = lib.rnerf_lpips_workspace_bytes(n, H, W)
-        if nb == 0:
-            check(-1, "rnerf_lpips_workspace_bytes")
-        key = (dev.index, stream)
-        ws = _lpips_workspaces.get(key)
-        if ws is None or ws.numel() < nb:
-            ws = _lpips_workspaces[key] = torch.empty(nb, dtype=torch.uint8, device=dev)
+        ws = workspace("rnerf_lpips_workspace_bytes", n, H, W, device=dev, keep_for=stream)
         want_map = return_map or return_both
-        out_map = torch.empty(tuple(lead) + (H, W), dtype=torch.float32, device=dev) if want_map else None
-        value = torch.empty(tuple(lead), dtype=torch.float32, device=dev) if return_both or not return_map else None
+        out_map = torch.empty(lead + (H, W), dtype=torch.float32, device=dev) if want_map else None
+        value = torch.empty(lead, dtype=torch.float32, device=dev) if return_both or not return_map else None
         shapes = lpips_layer_shapes(H, W)
         layers = torch.empty((n, sum(h * w for h, w in shapes)), dtype=torch.float32, device=dev) if return_layers else None
         check(lib.rnerf_lpips(ptr(x), ptr(y), n, H, W, ptr(wt), ptr(out_map), ptr(value), ptr(layers), ptr(ws), stream), "rnerf_lpips")
@@ -764,23 +770,9 @@ def lpips(a: torch.Tensor, b: torch.Tensor, weights, return_both: bool = False, 
         return res
     views, at = [], 0
     for h, w in shapes:
-        views.append(layers[:, at:at + h * w].reshape(tuple(lead) + (h, w)))
+        views.append(layers[:, at:at + h * w].reshape(lead + (h, w)))
         at += h * w
     return (res + (views,)) if return_both else (res, views)
-
-
-def _image_pair(a: torch.Tensor, b: torch.Tensor, what: str):
-    if tuple(a.shape) != tuple(b.shape):
-        raise ValueError(f"{what}: the images differ in shape: {tuple(a.shape)} vs {tuple(b.shape)}")
-    if a.dim() < 3:
-        raise ValueError(f"{what}: need [..., H, W, C] images, got shape {tuple(a.shape)}")
-    if a.device != b.device:
-        raise ValueError(f"{what}: the images are on different devices ({a.device}, {b.device})")
-    *lead, H, W, Ch = (int(s) for s in a.shape)
-    n = 1
-    for s in lead:
-        n *= s
-    return _chk(a, "reference"), _chk(b, "test"), tuple(lead), n, H, W, Ch
 
 
 def errmap_mse(reference: torch.Tensor, test: torch.Tensor, *, want_map: bool = True, want_mean: bool = True):
@@ -799,10 +791,7 @@ def errmap_mse(reference: torch.Tensor, test: torch.Tensor, *, want_map: bool = 
         mean, ws = None, None
         if want_mean:
             mean = torch.empty(lead, dtype=torch.float32, device=dev)
-            nb = lib.rnerf_errmap_mse_workspace_bytes(n, H, W)
-            if nb == 0:
-                check(-1, "rnerf_errmap_mse_workspace_bytes")
-            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            ws = workspace("rnerf_errmap_mse_workspace_bytes", n, H, W, device=dev)
         check(lib.rnerf_errmap_mse(ptr(a), ptr(b), n, H, W, Ch, ptr(out_map), ptr(mean), ptr(ws), torch.cuda.current_stream(dev).cuda_stream),
               "rnerf_errmap_mse")
     return out_map, mean
@@ -826,10 +815,7 @@ def ssim_summary(img0: torch.Tensor, img1: torch.Tensor, *, data_range: float = 
     lib = _lib.load()
     dev = a.device
     with torch.cuda.device(dev):
-        nb = lib.rnerf_ssim_summary_workspace_bytes(n, H, W, Ch, fs)
-        if nb == 0:
-            check(-1, "rnerf_ssim_summary_workspace_bytes")
-        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        ws = workspace("rnerf_ssim_summary_workspace_bytes", n, H, W, Ch, fs, device=dev)
         out_map = torch.empty(lead + (H - fs + 1, W - fs + 1), dtype=torch.float32, device=dev) if want_map else None
         mean = torch.empty(lead, dtype=torch.float32, device=dev) if want_mean else None
         check(lib.rnerf_ssim_summary(ptr(a), ptr(b), n, H, W, Ch, fs, float(filter_sigma), float(data_range), ptr(out_map), ptr(mean), ptr(ws),
@@ -872,19 +858,25 @@ def _vis_plane(t, name: str) -> torch.Tensor:
     return _chk(t, name)
 
 
-def vis_depth(depth: torch.Tensor, acc: Optional[torch.Tensor] = None, *, near: Optional[float] = None, far: Optional[float] = None,
-              ignore_frac: float = 0.0, curve: str = "neg_log", modulus: float = 0.0, want_rgb: bool = True, want_value: bool = False,
-              want_range: bool = False):
-    """visualize_depth (rnerf/vis.py:45-111) on the device (rnerf_vis_depth).  depth, acc (None = all ones): float32 device tensors
-    [H, W]; near / far: None = automatic.  -> (rgb [H, W, 3], value [H, W], range [2] = (near, far) before the curve), None for what was
-    not wanted.  Issued on the current stream of depth's device; nothing is synchronised."""
+def _vis_planes(depth, acc, what: str):
+    """-> (depth, acc or None, H, W), acc checked against depth."""
     d = _vis_plane(depth, "depth")
     H, W = int(d.shape[0]), int(d.shape[1])
     a = None
     if acc is not None:
         a = _vis_plane(acc, "acc")
         if tuple(a.shape) != (H, W) or a.device != d.device:
-            raise ValueError(f"vis_depth: acc {tuple(a.shape)} on {a.device} does not match depth {(H, W)} on {d.device}")
+            raise ValueError(f"{what}: acc {tuple(a.shape)} on {a.device} does not match depth {(H, W)} on {d.device}")
+    return d, a, H, W
+
+
+def vis_depth(depth: torch.Tensor, acc: Optional[torch.Tensor] = None, *, near: Optional[float] = None, far: Optional[float] = None,
+              ignore_frac: float = 0.0, curve: str = "neg_log", modulus: float = 0.0, want_rgb: bool = True, want_value: bool = False,
+              want_range: bool = False):
+    """visualize_depth (rnerf/vis.py:45-111) on the device (rnerf_vis_depth).  depth, acc (None = all ones): float32 device tensors
+    [H, W]; near / far: None = automatic.  -> (rgb [H, W, 3], value [H, W], range [2] = (near, far) before the curve), None for what was
+    not wanted.  Issued on the current stream of depth's device; nothing is synchronised."""
+    d, a, H, W = _vis_planes(depth, acc, "vis_depth")
     if curve not in _lib.VIS_CURVES:
         raise ValueError(f"vis_depth: curve must be one of {sorted(_lib.VIS_CURVES)}, got {curve!r}")
     if not (want_rgb or want_value or want_range):
@@ -894,12 +886,7 @@ def vis_depth(depth: torch.Tensor, acc: Optional[torch.Tensor] = None, *, near: 
     lib = _lib.load()
     dev = d.device
     with torch.cuda.device(dev):
-        ws = None
-        if n != n or f != f:
-            nb = lib.rnerf_vis_depth_workspace_bytes(H, W, frac)
-            if nb == 0:
-                check(-1, "rnerf_vis_depth_workspace_bytes")
-            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        ws = workspace("rnerf_vis_depth_workspace_bytes", H, W, frac, device=dev) if n != n or f != f else None
         rgb = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if want_rgb else None
         value = torch.empty((H, W), dtype=torch.float32, device=dev) if want_value else None
         rng = torch.empty(2, dtype=torch.float32, device=dev) if want_range else None
@@ -913,24 +900,13 @@ def vis_normals(depth: torch.Tensor, acc: Optional[torch.Tensor] = None, *, scal
     """visualize_normals / depth_to_normals (rnerf/vis.py:34-42, 114-132) on the device (rnerf_vis_normals).  depth, acc (None = no
     blend): float32 device tensors [H, W]; scaling: None = automatic.  -> (rgb [H, W, 3], normals [H, W, 3]), None for what was not
     wanted.  Issued on the current stream of depth's device; nothing is synchronised."""
-    d = _vis_plane(depth, "depth")
-    H, W = int(d.shape[0]), int(d.shape[1])
-    a = None
-    if acc is not None:
-        a = _vis_plane(acc, "acc")
-        if tuple(a.shape) != (H, W) or a.device != d.device:
-            raise ValueError(f"vis_normals: acc {tuple(a.shape)} on {a.device} does not match depth {(H, W)} on {d.device}")
+    d, a, H, W = _vis_planes(depth, acc, "vis_normals")
     if not (want_rgb or want_normals):
         raise ValueError("vis_normals: nothing wanted")
     lib = _lib.load()
     dev = d.device
     with torch.cuda.device(dev):
-        ws = None
-        if scaling is None:
-            nb = lib.rnerf_vis_normals_workspace_bytes(H, W)
-            if nb == 0:
-                check(-1, "rnerf_vis_normals_workspace_bytes")
-            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        ws = workspace("rnerf_vis_normals_workspace_bytes", H, W, device=dev) if scaling is None else None
         rgb = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if want_rgb else None
         normals = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if want_normals else None
         check(lib.rnerf_vis_normals(ptr(d), ptr(a), H, W, float("nan") if scaling is None else float(scaling), ptr(rgb), ptr(normals), ptr(ws),

@@ -89,23 +89,10 @@ def compute_ssim(img0, img1, max_val, filter_size=11, filter_sigma=1.5, k1=0.01,
         raise ValueError(f"compute_ssim: filter_size must be in [1, 31], got {filter_size}")
     if s0[-3] < filter_size or s0[-2] < filter_size:
         raise ValueError(f"compute_ssim: the images ({s0[-3]} x {s0[-2]}) are smaller than the window (filter_size {filter_size})")
-
-    def on_device(t):
-        return isinstance(t, torch.Tensor) and t.is_cuda
-    if on_device(img0):
-        dev = img0.device
-    elif on_device(img1):
-        dev = img1.device
-    else:
-        dev = torch.device("cuda", torch.cuda.current_device())
-
-    def as_f32(t):
-        if not isinstance(t, torch.Tensor):
-            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float32)))
-        return t.to(device=dev, dtype=torch.float32)
     from . import ops
-    a, b = as_f32(img0), as_f32(img1)
-    return ops.ssim(a, b, max_val=max_val, filter_size=filter_size, filter_sigma=filter_sigma, k1=k1, k2=k2, return_map=return_map)
+    dev = ops.device_of(img0, img1)
+    return ops.ssim(ops.as_f32(img0, dev), ops.as_f32(img1, dev), max_val=max_val, filter_size=filter_size, filter_sigma=filter_sigma, k1=k1, k2=k2,
+                    return_map=return_map)
 
 
 FLIP_PPD_DEFAULT = (0.7 * 3840 / 0.7) * math.pi / 180      # compute_ldrflip's default (flip_api.py:439): a 0.7 m wide 4K monitor at 0.7 m
@@ -128,22 +115,9 @@ def compute_flip(reference, test, pixels_per_degree=None, return_map=False):
     ppd = FLIP_PPD_DEFAULT if pixels_per_degree is None else float(pixels_per_degree)
     if not (ppd > 0.0 and math.isfinite(ppd)):
         raise ValueError(f"compute_flip: pixels_per_degree must be finite and > 0, got {pixels_per_degree}")
-
-    def on_device(t):
-        return isinstance(t, torch.Tensor) and t.is_cuda
-    if on_device(reference):
-        dev = reference.device
-    elif on_device(test):
-        dev = test.device
-    else:
-        dev = torch.device("cuda", torch.cuda.current_device())
-
-    def as_f32(t):
-        if not isinstance(t, torch.Tensor):
-            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float32)))
-        return t.to(device=dev, dtype=torch.float32)
     from . import ops
-    return ops.flip(as_f32(reference), as_f32(test), pixels_per_degree=ppd, return_map=return_map)
+    dev = ops.device_of(reference, test)
+    return ops.flip(ops.as_f32(reference, dev), ops.as_f32(test, dev), pixels_per_degree=ppd, return_map=return_map)
 
 
 def compute_lpips(img0, img1, weights, return_map=False):
@@ -158,14 +132,8 @@ def compute_lpips(img0, img1, weights, return_map=False):
         raise ValueError(f"compute_lpips: the images differ in shape: {s0} vs {s1}")
     if len(s0) not in (3, 4) or s0[-1] != 3:
         raise ValueError(f"compute_lpips: need [H, W, 3] or [n, H, W, 3] images, got shape {s0}")
-    dev = weights.device
-
-    def as_f32(t):
-        if not isinstance(t, torch.Tensor):
-            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float32)))
-        return t.to(device=dev, dtype=torch.float32)
     from . import ops
-    return ops.lpips(as_f32(img0), as_f32(img1), weights, return_map=return_map)
+    return ops.lpips(ops.as_f32(img0, weights.device), ops.as_f32(img1, weights.device), weights, return_map=return_map)
 
 
 def save_img(img, pth, to8b=True):

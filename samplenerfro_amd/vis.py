@@ -7,27 +7,11 @@ from __future__ import annotations
 
 import math
 
-import numpy as np
 import torch
 
 from . import _lib, ops
 
 CURVES = tuple(_lib.VIS_CURVES)          # the choices the reference's docstring names (vis.py:62-65), "neg_log" its default
-
-
-def _device_of(*xs) -> torch.device:
-    for x in xs:
-        if isinstance(x, torch.Tensor) and x.is_cuda:
-            return x.device
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _as_f32(t, dev: torch.device):
-    if t is None:
-        return None
-    if not isinstance(t, torch.Tensor):
-        t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float32)))
-    return t.to(device=dev, dtype=torch.float32)
 
 
 def _bound(v):
@@ -38,14 +22,14 @@ def _bound(v):
 def sinebow(h):
     """vis.py:23-26: a cyclic and uniform colour map, sin(pi x)^2 at 3/6 - h, 5/6 - h, 7/6 - h -> [..., 3].  The kernel has this built in
     for modulus > 0; this is the same map for use as a `colormap`."""
-    h = _as_f32(h, _device_of(h))
+    h = ops.as_f32(h, ops.device_of(h))
     f = lambda x: torch.sin(math.pi * x) ** 2
     return torch.stack([f(3 / 6 - h), f(5 / 6 - h), f(7 / 6 - h)], -1)
 
 
 def depth_to_normals(depth):
     """vis.py:34-42: `depth` [H, W] taken as orthographic -> normals [H, W, 3] (true 3 x 3 convolutions with zero padding)."""
-    d = _as_f32(depth, _device_of(depth))
+    d = ops.as_f32(depth, ops.device_of(depth))
     return ops.vis_normals(d, None, scaling=1.0, want_rgb=False, want_normals=True)[1]
 
 
@@ -63,8 +47,8 @@ def visualize_depth(depth, acc=None, near=None, far=None, ignore_frac=0, curve_f
         raise ValueError(f"visualize_depth: curve_fn must be one of {list(CURVES)}, got {curve_fn!r}")
     if colormap is not None and not callable(colormap):
         raise TypeError("visualize_depth: colormap must be None or a callable on a device tensor")
-    dev = _device_of(depth, acc)
-    d, a = _as_f32(depth, dev), _as_f32(acc, dev)
+    dev = ops.device_of(depth, acc)
+    d, a = ops.as_f32(depth, dev), ops.as_f32(acc, dev)
     kw = dict(near=_bound(near), far=_bound(far), ignore_frac=float(ignore_frac), curve=curve_fn, modulus=float(modulus))
     if colormap is None:
         return ops.vis_depth(d, a, **kw)[0]
@@ -82,12 +66,12 @@ def visualize_depth(depth, acc=None, near=None, far=None, ignore_frac=0, curve_f
 def visualize_normals(depth, acc, scaling=None):
     """vis.py:114-132 -> rgb [H, W, 3]: the fake normals of `depth`, scaled to be isotropic unless `scaling` is given, as colours, blended
     with acc unless it is None."""
-    dev = _device_of(depth, acc)
-    return ops.vis_normals(_as_f32(depth, dev), _as_f32(acc, dev), scaling=None if scaling is None else float(scaling))[0]
+    dev = ops.device_of(depth, acc)
+    return ops.vis_normals(ops.as_f32(depth, dev), ops.as_f32(acc, dev), scaling=None if scaling is None else float(scaling))[0]
 
 
 def visualize_suite(depth, acc):
     """vis.py:135-142 -> {"depth", "depth_mod" (modulus 0.1), "depth_normals"}, each [H, W, 3].  Seven launches."""
-    dev = _device_of(depth, acc)
-    d, a = _as_f32(depth, dev), _as_f32(acc, dev)
+    dev = ops.device_of(depth, acc)
+    d, a = ops.as_f32(depth, dev), ops.as_f32(acc, dev)
     return {"depth": ops.vis_depth(d, a)[0], "depth_mod": ops.vis_depth(d, a, modulus=0.1)[0], "depth_normals": ops.vis_normals(d, a)[0]}

@@ -21,7 +21,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import Grid, check, current_stream, ptr
 
 CHUNK_BYTES = 1 << 30        # default views_per_chunk: as many mask bytes per upload
@@ -137,15 +137,12 @@ def carve(masks, cam_mat, transforms, num_voxels: int, min_point=None, max_point
     nmin, nmax = [float(v) for v in min_point], [float(v) for v in max_point]
     G = int(num_voxels)
     lib = _lib.load()
-    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    device = ops.device_of(device=device)
     spec = Grid.make([G] * 3, nmin, nmax)
     chunk = int(views_per_chunk) if views_per_chunk else max(1, CHUNK_BYTES // (H * W))
     chunk = max(1, min(chunk, V))
-    ws_bytes = lib.rnerf_visual_hull_workspace_bytes(chunk, H, W)
-    if ws_bytes == 0:
-        check(-1, "rnerf_visual_hull_workspace_bytes")
+    workspace = ops.workspace("rnerf_visual_hull_workspace_bytes", chunk, H, W, device=device)
     with torch.cuda.device(device):
-        workspace = torch.empty(ws_bytes // 4, dtype=torch.int32, device=device)
         count = torch.empty((G, G, G), dtype=torch.int32, device=device)
         out = torch.empty((G, G, G), dtype=torch.float32, device=device)
         for v0 in range(0, V, chunk):
