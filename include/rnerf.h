@@ -38,9 +38,10 @@ extern "C" {
  * 4: the opt-in schedule fields no caller set are gone.  rnerf_train_cfg ends with aux_stream, grads_stream (nothing in between);
  * rnerf_prefetch ends with side_stream (the march always forks right before the last NerfMLP wgrad); rnerf_bkgd_backward is the only
  * background-MLP backward entry point.  Still 4 with rnerf_flip / rnerf_flip_workspace_bytes, rnerf_visual_hull_*, rnerf_marching_cubes_*,
- * rnerf_mesh_depth, rnerf_mask_dilate, rnerf_vis_*, rnerf_images_prepare, rnerf_errmap_*, rnerf_ssim_summary, rnerf_lpips and
- * rnerf_components_*: they are appended, no
- * existing entry point or struct moved. */
+ * rnerf_mesh_depth, rnerf_mask_dilate, rnerf_vis_*, rnerf_images_prepare, rnerf_errmap_*, rnerf_ssim_summary, rnerf_lpips,
+ * rnerf_components_* and rnerf_march_sparse: they are appended, no
+ * existing entry point or struct moved (rnerf_prefetch grew by two trailing fields: a caller that fills it by name and zeroes the
+ * rest gets the dense march as before). */
 #define RNERF_VERSION 4
 
 enum rnerf_status {
@@ -161,6 +162,14 @@ int rnerf_grid_query(const float* table, const rnerf_grid* g, const float* pts, 
 int rnerf_march(const float* table, const rnerf_grid* g, const float* origins, const float* viewdirs, int32_t B,
                 double near, double far, int32_t num_nodes, float* path_pd, float* path_dr, float* path_ior,
                 int32_t* vox, void* stream);
+/* rnerf_march that records the sampled nodes only (appended; RNERF_VERSION stays 4).  sample_nodes: device int32[num_nodes / num_path],
+ * one node per group of num_path consecutive nodes (the jitter of rnerf_rng_forward); node k is recorded where
+ * sample_nodes[k / num_path] == k, with the bits rnerf_march writes there (position, normalised direction, distance), and every other
+ * record of path_pd / path_dr is left as it was: only a consumer that reads the path through this very array may use it (a flat model:
+ * num_fine == 0).  num_nodes must be a multiple of num_path.  sample_nodes == NULL: every node, as rnerf_march. */
+int rnerf_march_sparse(const float* table, const rnerf_grid* g, const float* origins, const float* viewdirs, int32_t B,
+                       double near, double far, int32_t num_nodes, float* path_pd, float* path_dr,
+                       const int32_t* sample_nodes, int32_t num_path, void* stream);
 
 /* ---- N1 weights: pack a flat fp32 NerfMLP parameter buffer into the MFMA operand stream of `precision`. */
 size_t rnerf_nerfmlp_packed_bytes(int precision);
@@ -497,6 +506,12 @@ typedef struct rnerf_prefetch {
   float* path_pd;              /* float4[N][B] each: where the next batch's path record goes */
   float* path_dr;
   void* side_stream;
+  /* Appended (RNERF_VERSION stays 4: the binding that fills this struct ships with the library).  Both null: every node is recorded.
+   * Both given (flat models only): next_keys4 = the device uint32[4] (key_0, key_1) the NEXT step will pass as keys4; the call runs
+   * rnerf_rng_forward on it on the side stream into sample_nodes (device int32[N_c]) and marches with rnerf_march_sparse.  The next step
+   * must then read the path through exactly that array (its jitter_override). */
+  const uint32_t* next_keys4;
+  int32_t* sample_nodes;
 } rnerf_prefetch;
 size_t rnerf_train_workspace_bytes(const rnerf_model* m, const rnerf_train_cfg* c, int32_t B);
 int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_train_cfg* c, const float* theta, const float* origins, const float* viewdirs,

@@ -77,7 +77,8 @@ class AdamCfg(C.Structure):
 
 class Prefetch(C.Structure):
     """rnerf_prefetch: the next batch's march on a side stream, forked right before the last wgrad of rnerf_train_forward_backward."""
-    _fields_ = [("origins", C.c_void_p), ("viewdirs", C.c_void_p), ("path_pd", C.c_void_p), ("path_dr", C.c_void_p), ("side_stream", C.c_void_p)]
+    _fields_ = [("origins", C.c_void_p), ("viewdirs", C.c_void_p), ("path_pd", C.c_void_p), ("path_dr", C.c_void_p), ("side_stream", C.c_void_p),
+                ("next_keys4", C.c_void_p), ("sample_nodes", C.c_void_p)]
 
 
 LEVEL_FLOATS = 9
@@ -96,6 +97,7 @@ SIGNATURES = {
     "rnerf_grid_build_table": (C.c_int, [_vp, _vp, _GP, _vp]),
     "rnerf_grid_query": (C.c_int, [_vp, _GP, _vp, _i64, _vp, _vp, _vp]),
     "rnerf_march": (C.c_int, [_vp, _GP, _vp, _vp, _i32, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "rnerf_march_sparse": (C.c_int, [_vp, _GP, _vp, _vp, _i32, _dbl, _dbl, _i32, _vp, _vp, _vp, _i32, _vp]),
     "rnerf_nerfmlp_packed_bytes": (C.c_size_t, [C.c_int]),
     "rnerf_nerfmlp_pack": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "rnerf_nerfmlp_forward": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),

@@ -42,12 +42,20 @@ __device__ __forceinline__ void march_chunk_barrier() { asm volatile("s_waitcnt 
 
 // BRICKS: the table is in 2x2x2-brick order (rnerf_table_layout): two more integer instructions per gathered index, ~40 % fewer new cache
 // lines per step on a table that does not fit the caches.
-template <bool WANT_IOR, bool WANT_VOX, bool BRICKS>
+//
+// SPARSE: the recorder writes the record of node k only where sample_nodes[k / num_path] == k (the step's jitter: one node per group of
+// num_path) and leaves every other record of the buffer untouched.  A flat model reads a path through its jitter only, so 1 - 1/P of
+// the records (184 of 201 MB per march at 1536 nodes x 4096 rays) were written and never read — beside the HBM-paced wgrad whose
+// CUs the next batch's march shares.  The travelled distance is an ordered sum over ALL nodes and keeps its sqrt at every node; the
+// direction's normalisation (a sqrt + a division) and the two stores run at the sampled nodes only.  The test is wave-uniform: one
+// scalar load per group.  The marcher wave, the ring and the barriers are the dense kernel's; the written records are its bits.
+template <bool WANT_IOR, bool WANT_VOX, bool BRICKS, bool SPARSE>
 __global__ void __launch_bounds__(128) march_kernel(const float* __restrict__ table, MarchParams g,
                                                     const float* __restrict__ origins, const float* __restrict__ viewdirs,
                                                     int B, float near, float step, int num_nodes,
                                                     float* __restrict__ path_pd, float* __restrict__ path_dr,
-                                                    float* __restrict__ path_ior, int* __restrict__ vox, int rays_per_wg) {
+                                                    float* __restrict__ path_ior, int* __restrict__ vox, int rays_per_wg,
+                                                    const int* __restrict__ sample_nodes, int num_path) {
   constexpr int C = kMarchChunk;
   __shared__ float2 ring[2][C][64];               // (p, d) of the lane's coordinate, per node
   const int lane = threadIdx.x & 63;
@@ -67,6 +75,9 @@ __global__ void __launch_bounds__(128) march_kernel(const float* __restrict__ ta
     float* __restrict__ out_pd = path_pd + 4 * (size_t)r + q;          // advanced by one node (B records) per node
     float* __restrict__ out_dr = path_dr + 4 * (size_t)r + q;
     float rt = near, p_prev = 0.f;
+    // SPARSE: `wanted` = the sampled node of the group node k is in, `left` = nodes of that group from k on (both wave-uniform)
+    int group = 0, left = num_path, wanted = 0;
+    if constexpr (SPARSE) wanted = sample_nodes[0];
     for (int c = 0; c < nchunks; ++c) {
       march_chunk_barrier();                                           // chunk c is in the ring
       const float2* __restrict__ src = &ring[c & 1][0][lane];
@@ -78,10 +89,18 @@ __global__ void __launch_bounds__(128) march_kernel(const float* __restrict__ ta
         const float p = v.x, d = v.y;
         if (k > 0) rt = fadd(rt, fsqrt(quad_sumsq3(fsub(p_prev, p))));
         p_prev = p;
-        const float nrm = fsqrt(fmaxf(quad_sumsq3(d), 1e-6f));
-        *out_pd = q < 3 ? p : rt;
-        *out_dr = q < 3 ? fdiv(d, nrm) : 0.f;
+        if (!SPARSE || k == wanted) {
+          const float nrm = fsqrt(fmaxf(quad_sumsq3(d), 1e-6f));
+          *out_pd = q < 3 ? p : rt;
+          *out_dr = q < 3 ? fdiv(d, nrm) : 0.f;
+        }
         out_pd += node_stride; out_dr += node_stride;
+        if constexpr (SPARSE) {
+          if (--left == 0) {                                             // the next node opens a group (none behind the last: nothing is read)
+            left = num_path; ++group;
+            wanted = (group + 1) * num_path <= num_nodes ? sample_nodes[group] : -1;
+          }
+        }
       }
     }
     return;
@@ -184,9 +203,9 @@ __global__ void __launch_bounds__(128) march_kernel(const float* __restrict__ ta
 
 using namespace rnerf;
 
-extern "C" int rnerf_march(const float* table, const rnerf_grid* g, const float* origins, const float* viewdirs,
-                           int32_t B, double near, double far, int32_t num_nodes, float* path_pd, float* path_dr,
-                           float* path_ior, int32_t* vox, void* stream) {
+static int march_impl(const float* table, const rnerf_grid* g, const float* origins, const float* viewdirs,
+                      int32_t B, double near, double far, int32_t num_nodes, float* path_pd, float* path_dr,
+                      float* path_ior, int32_t* vox, const int32_t* sample_nodes, int32_t num_path, void* stream) {
   RNERF_CHECK_ARG(table && g && origins && viewdirs && path_pd && path_dr, "rnerf_march: null pointer");
   RNERF_CHECK_ARG(B > 0 && num_nodes >= 2, "rnerf_march: need B > 0 and num_nodes >= 2");
   RNERF_CHECK_ARG((((uintptr_t)table | (uintptr_t)path_pd | (uintptr_t)path_dr | (uintptr_t)path_ior) & 15) == 0,
@@ -208,10 +227,17 @@ extern "C" int rnerf_march(const float* table, const rnerf_grid* g, const float*
   const dim3 block(128), grid((B + rpw - 1) / rpw);
   hipStream_t st = (hipStream_t)stream;
 #define LAUNCH2(I, V, K)                                                                                           \
-  hipLaunchKernelGGL((march_kernel<I, V, K>), grid, block, 0, st, table, p, origins, viewdirs, B, nearf, stepf, num_nodes, \
-                     path_pd, path_dr, path_ior, vox, rpw)
+  hipLaunchKernelGGL((march_kernel<I, V, K, false>), grid, block, 0, st, table, p, origins, viewdirs, B, nearf, stepf, num_nodes, \
+                     path_pd, path_dr, path_ior, vox, rpw, (const int*)nullptr, 0)
 #define LAUNCH(I, V) do { if (gp.layout == RNERF_TABLE_BRICKS) LAUNCH2(I, V, true); else LAUNCH2(I, V, false); } while (0)
-  if (path_ior && vox) LAUNCH(true, true);
+  if (sample_nodes) {
+    if (gp.layout == RNERF_TABLE_BRICKS)
+      hipLaunchKernelGGL((march_kernel<false, false, true, true>), grid, block, 0, st, table, p, origins, viewdirs, B, nearf, stepf, num_nodes,
+                         path_pd, path_dr, path_ior, vox, rpw, sample_nodes, num_path);
+    else
+      hipLaunchKernelGGL((march_kernel<false, false, false, true>), grid, block, 0, st, table, p, origins, viewdirs, B, nearf, stepf, num_nodes,
+                         path_pd, path_dr, path_ior, vox, rpw, sample_nodes, num_path);
+  } else if (path_ior && vox) LAUNCH(true, true);
   else if (path_ior) LAUNCH(true, false);
   else if (vox) LAUNCH(false, true);
   else LAUNCH(false, false);
@@ -219,4 +245,18 @@ extern "C" int rnerf_march(const float* table, const rnerf_grid* g, const float*
 #undef LAUNCH2
   RNERF_CHECK_LAUNCH();
   return RNERF_OK;
+}
+
+extern "C" int rnerf_march(const float* table, const rnerf_grid* g, const float* origins, const float* viewdirs,
+                           int32_t B, double near, double far, int32_t num_nodes, float* path_pd, float* path_dr,
+                           float* path_ior, int32_t* vox, void* stream) {
+  return march_impl(table, g, origins, viewdirs, B, near, far, num_nodes, path_pd, path_dr, path_ior, vox, nullptr, 0, stream);
+}
+
+extern "C" int rnerf_march_sparse(const float* table, const rnerf_grid* g, const float* origins, const float* viewdirs,
+                                  int32_t B, double near, double far, int32_t num_nodes, float* path_pd, float* path_dr,
+                                  const int32_t* sample_nodes, int32_t num_path, void* stream) {
+  RNERF_CHECK_ARG(!sample_nodes || (num_path >= 1 && num_nodes % num_path == 0),
+                  "rnerf_march_sparse: sample_nodes needs num_path >= 1 and num_nodes a multiple of num_path");
+  return march_impl(table, g, origins, viewdirs, B, near, far, num_nodes, path_pd, path_dr, nullptr, nullptr, sample_nodes, num_path, stream);
 }

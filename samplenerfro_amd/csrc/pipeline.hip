@@ -622,7 +622,10 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
     if (!jitter_override) jitter = t.jitter;
   }
   if (!path_pd) {
-    RNERF_TRY(rnerf_march(m->table, &m->grid, origins, viewdirs, B, m->near, m->far, N, f.path_pd, f.path_dr, nullptr, nullptr, stream));
+    // a flat model reads the path through the jitter only: the march records those nodes and no others (the step's own draw: one node
+    // per group of num_path; an injected jitter may be any increasing sequence and gets every node)
+    const int32_t* sampled = (Nf == 0 && keys4 && !jitter_override) ? t.jitter : nullptr;
+    RNERF_TRY(rnerf_march_sparse(m->table, &m->grid, origins, viewdirs, B, m->near, m->far, N, f.path_pd, f.path_dr, sampled, m->num_path, stream));
     path_pd = f.path_pd; path_dr = f.path_dr;
   }
   hipLaunchKernelGGL(bkgd_dirs_kernel, dim3((B + M + 255) / 256), dim3(256), 0, st, (const float4*)path_dr, jitter, Nc, B, env_dirs, M, (float4*)f.bk_dirs);
@@ -672,9 +675,14 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
   // whole march hides behind that HBM-paced kernel.
   auto march_next = [&]() -> int {
     RNERF_CHECK_ARG(next->origins && next->viewdirs && next->path_pd && next->path_dr && next->side_stream, "rnerf_train_forward_backward: incomplete rnerf_prefetch");
+    RNERF_CHECK_ARG((next->next_keys4 == nullptr) == (next->sample_nodes == nullptr), "rnerf_train_forward_backward: rnerf_prefetch needs both next_keys4 and sample_nodes or neither");
+    RNERF_CHECK_ARG(!next->sample_nodes || Nf == 0, "rnerf_train_forward_backward: rnerf_prefetch.sample_nodes is for flat models (num_fine == 0) only");
     RNERF_TRY(rnerf_fork(stream, next->side_stream));
-    return rnerf_march(m->table, &m->grid, next->origins, next->viewdirs, B, m->near, m->far, N, next->path_pd, next->path_dr, nullptr, nullptr,
-                       next->side_stream);
+    // the next step's jitter from the next step's keys, then only its nodes: 1 / num_path of the record's bytes beside the HBM-paced wgrad
+    if (next->sample_nodes)
+      RNERF_TRY(rnerf_rng_forward(next->next_keys4, Nc, m->num_path, c->use_random_choice, next->sample_nodes, nullptr, next->side_stream));
+    return rnerf_march_sparse(m->table, &m->grid, next->origins, next->viewdirs, B, m->near, m->far, N, next->path_pd, next->path_dr,
+                              next->sample_nodes, m->num_path, next->side_stream);
   };
   // ---- backward, last level first ----
   if (aux) RNERF_TRY(rnerf_join(stream, aux));

@@ -285,9 +285,10 @@ class NerfModel:
             ev.record(self._side)
         return PathHandle(pd, dr, ior, ev, rays.origins.shape[0])
 
-    def prefetch_slot(self, rays: Rays):
+    def prefetch_slot(self, rays: Rays, next_keys=None):
         """A PathHandle whose march rnerf_train_forward_backward issues itself (rnerf_prefetch): buffers + descriptor; the caller records
-        handle.event on the side stream after the call."""
+        handle.event on the side stream after the call.  next_keys = (key_0, key_1) of the step that will consume the path (flat models):
+        the march draws that step's jitter into a buffer of the handle and records only its nodes (a sparse handle)."""
         if not self.stage.startswith("radiance"):
             raise NotImplementedError("prefetch: the all* march depends on the so3_mlp parameters")
         if self._side is None:
@@ -300,7 +301,18 @@ class NerfModel:
             t.record_stream(self._side)
         h = PathHandle(pd, dr, None, torch.cuda.Event(), B)
         h.keep = (o, v)
-        return h, _lib.Prefetch(o.data_ptr(), v.data_ptr(), pd.data_ptr(), dr.data_ptr(), self._side.cuda_stream)
+        nxt = _lib.Prefetch(o.data_ptr(), v.data_ptr(), pd.data_ptr(), dr.data_ptr(), self._side.cuda_stream)
+        if next_keys is not None:
+            if self.num_fine_samples > 0:
+                raise ValueError("prefetch_slot: a hierarchical model resamples arbitrary nodes and needs every record (next_keys=None)")
+            keys = self._keys_dev(*next_keys)
+            jit = torch.empty(self.num_coarse_samples, dtype=torch.int32, device=self.device)
+            keys.record_stream(self._side); jit.record_stream(self._side)
+            h.sparse, h.jitter, h.key = True, jit, np.array(next_keys[0], np.uint32).reshape(2).copy()
+            h.keep = (o, v, keys)
+            h._march_args = (self.table, self.spec, self.near, self.far, self.num_samples)      # what complete() marches the other nodes with
+            nxt.next_keys4, nxt.sample_nodes = keys.data_ptr(), jit.data_ptr()
+        return h, nxt
 
     def tail_stream(self) -> torch.cuda.Stream:
         """The stream rnerf_train_forward_backward uses for work that is independent of the NerfMLP backward (rnerf_train_cfg.aux_stream)."""
@@ -398,6 +410,7 @@ class NerfModel:
                 per_ray = 1
         pd = dr = None
         if path is not None:
+            path.need_dense("NerfModel.apply")
             if path.batch != B:
                 raise ValueError("path handle was marched for a different batch size")
             cur = torch.cuda.current_stream()
@@ -447,6 +460,7 @@ class NerfModel:
         sparsity = self.use_online_sparsity and (ctx is None or (bool(ctx.get("loss_sp")) and not self.stage.startswith("all")))
         want_ior = sparsity or (taps is not None and not (ctx is not None and self.stage.startswith("all")))
         if path is not None:
+            path.need_dense("NerfModel.apply")
             if path.batch != B:
                 raise ValueError("path handle was marched for a different batch size")
             cur = torch.cuda.current_stream()
@@ -634,10 +648,59 @@ def level_views(out: torch.Tensor, B: int):
 
 
 class PathHandle:
-    """A marched path record produced on the side stream (NerfModel.prefetch_path)."""
+    """A marched path record produced on the side stream (NerfModel.prefetch_path).
 
-    def __init__(self, pd, dr, ior, event, batch):
-        self.pd, self.dr, self.ior, self.event, self.batch = pd, dr, ior, event, batch
+    sparse: only the nodes in `jitter` (device int32[N_c], drawn from `key` = the key_0 of the step the path is for) hold records; the
+    rest of the buffers is whatever they held.  Such a path may be read through that very jitter only: train_step's flat product path
+    does, through raw(), after comparing `key` with the key it derives itself; model.apply refuses it (need_dense()).
+    `pd` / `dr` are the WHOLE record [N, B, 4], as they always were: read on a sparse handle they first complete it (complete())."""
+
+    def __init__(self, pd, dr, ior, event, batch, sparse=False, jitter=None, key=None):
+        self._pd, self._dr, self.ior, self.event, self.batch = pd, dr, ior, event, batch
+        self.sparse, self.jitter, self.key = bool(sparse), jitter, key
+        self._march_args = None
+
+    def raw(self):
+        """(pd, dr) as the march left them: on a sparse handle only the nodes in `jitter` hold records."""
+        return self._pd, self._dr
+
+    @property
+    def pd(self):
+        self.complete()
+        return self._pd
+
+    @property
+    def dr(self):
+        self.complete()
+        return self._dr
+
+    def complete(self) -> None:
+        """A sparse handle becomes a dense one: the nodes its march did not record are marched now, on the current stream (a stand-alone
+        dense march into scratch, copied to those nodes only — the records of `jitter`'s nodes stay the ones the prefetch wrote, which
+        are the same bits).  Not on any step's path: for callers that look at the record itself."""
+        if not self.sparse:
+            return
+        if self._march_args is None:
+            raise ValueError("this sparse path handle does not know its rays: it cannot be completed")
+        table, spec, near, far, N = self._march_args
+        cur = torch.cuda.current_stream()
+        cur.wait_event(self.event)
+        pd, dr, _, _ = ops.march(table, spec, self.keep[0], self.keep[1], near, far, N)
+        rest = torch.ones(N, dtype=torch.bool, device=pd.device)
+        rest[self.jitter.long()] = False
+        self._pd[rest] = pd[rest]
+        self._dr[rest] = dr[rest]
+        self._pd.record_stream(cur); self._dr.record_stream(cur)
+        self.sparse = False
+
+    def need_dense(self, who: str) -> None:
+        if self.sparse:
+            raise ValueError(f"{who}: this path handle holds the records of its own jitter's nodes only (a flat train step's prefetch); "
+                             "march the rays with prefetch_path() or pass path=None")
+
+    def matches(self, key_0) -> bool:
+        """A sparse path: was its jitter drawn from this key_0?"""
+        return self.key is not None and np.array_equal(np.asarray(self.key, np.uint32).reshape(-1), np.asarray(key_0, np.uint32).reshape(-1))
 
 
 def make_variables(flat: Dict[str, torch.Tensor]) -> Dict[str, Any]:

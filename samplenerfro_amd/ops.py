@@ -137,6 +137,25 @@ def march(table: torch.Tensor, spec: Grid, origins: torch.Tensor, viewdirs: torc
     return path_pd, path_dr, ior, vox
 
 
+def march_sparse(table: torch.Tensor, spec: Grid, origins: torch.Tensor, viewdirs: torch.Tensor, near: float, far: float,
+                 num_nodes: int, sample_nodes: Optional[torch.Tensor], num_path: int, out):
+    """rnerf_march_sparse: the march that records node k only where sample_nodes[k // num_path] == k (int32 [num_nodes // num_path] on the
+    device: a flat model's jitter) into out = (path_pd, path_dr) [N,B,4] and leaves their other records as they are.  sample_nodes None:
+    every node."""
+    lib = _lib.load()
+    table = _chk(table, "table"); o = _chk(origins, "origins"); d = _chk(viewdirs, "viewdirs")
+    path_pd, path_dr = out
+    B = o.shape[0]
+    if any(tuple(t.shape) != (num_nodes, B, 4) or not t.is_contiguous() for t in (path_pd, path_dr)):
+        raise ValueError("march_sparse: out must be two contiguous [num_nodes, B, 4] float32 tensors")
+    _chk(path_pd, "path_pd"); _chk(path_dr, "path_dr")
+    if sample_nodes is not None and (sample_nodes.dtype != torch.int32 or not sample_nodes.is_contiguous() or sample_nodes.numel() * int(num_path) != num_nodes):
+        raise ValueError("march_sparse: sample_nodes must be contiguous int32 [num_nodes // num_path]")
+    check(lib.rnerf_march_sparse(ptr(table), C.byref(spec), ptr(o), ptr(d), B, float(near), float(far), int(num_nodes),
+                                 ptr(path_pd), ptr(path_dr), ptr(sample_nodes), int(num_path), current_stream()), "rnerf_march_sparse")
+    return path_pd, path_dr
+
+
 def nerfmlp_pack(params_flat: torch.Tensor, precision: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Pack a flat fp32 NerfMLP parameter buffer (595844 floats, flax order) into the MFMA operand stream."""
     lib = _lib.load()

@@ -74,6 +74,23 @@ def randint(key, shape, minval: int, maxval: int) -> np.ndarray:
     return (np.int64(minval) + off.astype(np.int64)).astype(np.int32)
 
 
+def step_keys(rng):
+    """train_step's `rng, key_0, key_1 = random.split(rng, 3)` (train.py:74) -> (rng', key_0, key_1).  The keys of step k + 1 are
+    step_keys(rng' of step k)[1:]: a fixed function of what step k returns, so step k can derive them one step ahead."""
+    out = split(np.asarray(rng, np.uint32), 3)
+    return out[0], out[1], out[2]
+
+
+def step_jitter(key_0, num_coarse: int, num_path: int, use_random_choice: bool) -> np.ndarray:
+    """The jitter NerfModel.__call__ draws from a step's key_0 (rnerf/models.py:240-242): `key, rng_0 = split(key_0)`;
+    arange(0, N_c * P, P) (+ randint(key, [N_c], 0, P)).  What rnerf_rng_forward computes on the device."""
+    key, _ = split(np.asarray(key_0, np.uint32))
+    j = np.arange(0, num_coarse * num_path, num_path, dtype=np.int32)
+    if use_random_choice:
+        j = j + randint(key, (num_coarse,), 0, num_path)
+    return j.astype(np.int32)
+
+
 _ERFINV_CENTRAL = (2.81022636e-08, 3.43273939e-07, -3.5233877e-06, -4.39150654e-06, 0.00021858087, -0.00125372503, -0.00417768164,
                    0.246640727, 1.50140941)
 _ERFINV_TAIL = (-0.000200214257, 0.000100950558, 0.00134934322, -0.00367342844, 0.00573950773, -0.0076224613, 0.00943887047,

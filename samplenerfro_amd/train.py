@@ -320,10 +320,23 @@ def _adam_update_on_device(state: TrainState, flags) -> None:
     _bump(state.theta)
 
 
+def _split3(state: TrainState, rng, ahead: bool = False):
+    """prng.step_keys(rng) -> (rng', key_0, key_1).  ahead=True (the split of the NEXT step, made one step early for its sparse path) is
+    remembered with the state, so that the step it belongs to does not pay for it a second time."""
+    r = np.asarray(rng, np.uint32)
+    held = getattr(state, "_split_ahead", None)
+    if held is not None and np.array_equal(held[0], r):
+        return held[1]
+    out = prng.step_keys(r)
+    if ahead:
+        state._split_ahead = (r.copy(), out)
+    return out
+
+
 def _train_step_whole(model: NerfModel, rng, state: TrainState, batch, flags, jitter, u_fine, path, next_rays):
     """train_step for the radiance stages through the whole-path entry points (include/rnerf.h, csrc/pipeline.hip)."""
     lib = _lib.load()
-    rng, key_0, key_1 = prng.split(np.asarray(rng, np.uint32), 3)
+    rng, key_0, key_1 = _split3(state, rng)
     annealed = float(np.asarray(batch["annealed_alpha"]).reshape(-1)[0])
     rays: Rays = batch["rays"]
     o, v = ops._chk(rays.origins, "origins"), ops._chk(rays.viewdirs, "viewdirs")
@@ -343,13 +356,21 @@ def _train_step_whole(model: NerfModel, rng, state: TrainState, batch, flags, ji
     if u_fine is not None:
         u = ops._chk(u_fine, "u_fine"); per_ray = 1 if u.dim() == 2 else 0
     pd = dr = None
+    flat = model.num_fine_samples == 0
+    if path is not None and path.sparse and not (flat and jit is None and path.matches(key_0)):
+        # the path holds the nodes of a jitter this step does not draw (a re-seeded caller, an injected jitter): never read it with
+        # another one — the step marches its own rays, as without a handle
+        path = None
     if path is not None:
         if path.batch != B:
             raise ValueError("path handle was marched for a different batch size")
         cur = torch.cuda.current_stream()
         cur.wait_event(path.event)
-        pd, dr = path.pd, path.dr
+        pd, dr = path.raw()                        # (as the march left them: path.pd / path.dr would complete a sparse record first)
         pd.record_stream(cur); dr.record_stream(cur)
+        if path.sparse:                            # the array the march recorded by IS the step's jitter (the same draw from the same key)
+            jit = path.jitter
+            jit.record_stream(cur)
     ws = model._workspace("train", lib.rnerf_train_workspace_bytes(C.byref(m), C.byref(c), B))
     G = state.grads
     n_theta = state.theta.numel()
@@ -357,7 +378,10 @@ def _train_step_whole(model: NerfModel, rng, state: TrainState, batch, flags, ji
     # background-MLP backward, the loss tail, the all-reduce and the optimiser update
     nxt, next_path = None, None
     if next_rays is not None:
-        next_path, nxt = model.prefetch_slot(next_rays)
+        # a flat model reads a path through its jitter only, and the next step's jitter is a fixed function of the rng this step returns:
+        # its keys are derived here, one step ahead, and the march records the nodes of that draw alone (a sparse handle, which the next
+        # step uses only if the keys it derives itself are these)
+        next_path, nxt = model.prefetch_slot(next_rays, next_keys=_split3(state, rng, ahead=True)[1:] if flat else None)
     # jax.lax.pmean of gradients and stats (train.py:166-167).  With more than one rank the NerfMLP segments (95 % of the bytes) start their
     # all-reduce on a side stream the call orders behind the last wgrad; the background-MLP gradients and the stats (computed on the aux
     # stream beside that wgrad, joined inside the call) follow in a small second one.
@@ -604,6 +628,8 @@ def _train_step_once(model: NerfModel, rng, state: TrainState, batch: Dict[str, 
         # (rnerf_adam_update); what follows below is the same sequence stage by stage, with taps (parity tests, stage all*)
         return _train_step_whole(model, rng, state, batch, flags, jitter, u_fine, path, next_rays)
     rng, key_0, key_1 = prng.split(np.asarray(rng, np.uint32), 3)
+    if path is not None and path.sparse:
+        path = None                       # (a flat product step's prefetch: the nodes of one jitter only; this sequence wants the whole record)
     annealed = float(np.asarray(batch["annealed_alpha"]).reshape(-1)[0])
     rays: Rays = batch["rays"]
     pixels = batch["pixels"][..., :3].contiguous()

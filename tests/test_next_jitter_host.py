@@ -1,0 +1,71 @@
+"""The keys and the jitter of step k + 1, derived on the host in step k (train_step's sparse path prefetch): they must be what step k + 1
+derives itself from the rng step k returned — over a chain of steps, with and without use_random_choice."""
+import types
+
+import numpy as np
+import pytest
+
+from samplenerfro_amd import prng
+
+STEPS = 5
+
+
+def _own_jitter(key_0, Nc, P, use_random_choice):
+    """NerfModel.forward's own sequence: `key, rng_0 = split(rng_0)`; make_jitter(key)."""
+    key, _ = prng.split(np.asarray(key_0, np.uint32))
+    j = np.arange(0, Nc * P, P, dtype=np.int32)
+    if use_random_choice:
+        j = j + prng.randint(key, (Nc,), 0, P)
+    return j.astype(np.int32)
+
+
+@pytest.mark.parametrize("use_random_choice", [True, False])
+@pytest.mark.parametrize("seed,Nc,P", [(0, 128, 12), (20200823, 8, 4), (2 ** 40 + 17, 10, 5)])
+def test_keys_and_jitter_derived_one_step_ahead(seed, Nc, P, use_random_choice):
+    rng = prng.PRNGKey(seed)
+    ahead = None                                             # (key_0, key_1, jitter) step k - 1 derived for step k
+    seen = []
+    for _ in range(STEPS):
+        want = prng.split(np.asarray(rng, np.uint32), 3)     # train_step: rng, key_0, key_1 = split(rng, 3)
+        rng, key_0, key_1 = prng.step_keys(rng)
+        assert np.array_equal(rng, want[0]) and np.array_equal(key_0, want[1]) and np.array_equal(key_1, want[2])
+        jit = _own_jitter(key_0, Nc, P, use_random_choice)
+        if ahead is not None:
+            assert np.array_equal(ahead[0], key_0) and np.array_equal(ahead[1], key_1)
+            assert ahead[2].dtype == np.int32 and np.array_equal(ahead[2], jit)
+        assert np.all(jit // P == np.arange(Nc))             # one node per group of P: what the sparse march records by
+        seen.append(jit)
+        _, n0, n1 = prng.step_keys(rng)                      # one step ahead, from the rng this step returns
+        ahead = (n0, n1, prng.step_jitter(n0, Nc, P, use_random_choice))
+    if use_random_choice:
+        assert any(not np.array_equal(seen[0], s) for s in seen[1:])        # the draws do change from step to step
+    else:
+        assert all(np.array_equal(s, np.arange(0, Nc * P, P)) for s in seen)
+
+
+def test_the_split_made_ahead_is_reused_by_the_step_it_belongs_to():
+    """train._split3: the split of step k + 1 made in step k is handed to step k + 1 as it is; any other rng is split afresh."""
+    from samplenerfro_amd import train
+    state = types.SimpleNamespace()
+    rng = prng.PRNGKey(7)
+    rng1, k0, k1 = train._split3(state, rng)
+    ahead = train._split3(state, rng1, ahead=True)
+    again = train._split3(state, rng1)
+    assert all(a is b for a, b in zip(ahead, again))
+    for got, want in zip(again, prng.split(rng1, 3)):
+        assert np.array_equal(got, want)
+    other = train._split3(state, prng.PRNGKey(8))            # a re-seeded caller
+    for got, want in zip(other, prng.split(prng.PRNGKey(8), 3)):
+        assert np.array_equal(got, want)
+
+
+def test_a_sparse_handle_knows_its_key_and_refuses_dense_consumers():
+    from samplenerfro_amd.models import PathHandle
+    key = prng.PRNGKey(3)
+    h = PathHandle(None, None, None, None, 4, sparse=True, jitter=None, key=key)
+    assert h.matches(key.copy()) and not h.matches(prng.PRNGKey(4))
+    with pytest.raises(ValueError):
+        h.need_dense("test")
+    dense = PathHandle(None, None, None, None, 4)
+    dense.need_dense("test")
+    assert not dense.sparse and not dense.matches(key)
