@@ -867,6 +867,40 @@ int rnerf_components_stats(const int32_t* labels, const int32_t dims[3], int32_t
 int rnerf_components_apply(const int32_t* labels, const uint8_t* keep, double drop_value, const int32_t* fill_labels, const uint8_t* fill,
                            double fill_value, void* grid, int32_t dtype, const int32_t dims[3], void* stream);
 
+/* ---- A/B comparison of two runs: metric/compare.py and metric/export.py's export_video (csrc/errmap.hip) ------------------------------
+ * Appended; RNERF_VERSION stays 4.  The error maps of each run are those of the summary (rnerf_errmap_mse, rnerf_ssim_summary,
+ * rnerf_lpips, rnerf_flip); these two calls turn them, and the runs' 8-bit images, into finished bytes.
+ *
+ * rnerf_compare_sheet: compare.py:216-236 as bytes.  maps_a, maps_b, map_h, map_w: HOST arrays of 1 <= K <= 4 device pointers
+ * float[map_h[k]][map_w[k]] (the k-th error map of run A and of run B) with 1 <= map_h[k] <= H, 1 <= map_w[k] <= W; out: device
+ * uint8[H][K (W + 5)][3].  Per element (:221-223), with d = |a - b| one rounded float32 subtraction:
+ *   tie      d < float32(1e-3) (no float32 lies between 1e-3 and float32(1e-3): numpy's comparison with the Python float is the same set)
+ *   A wins   not a tie and a <= b        B wins   not a tie and a > b        neither   a NaN on either side
+ * inf - inf is NaN and so not a tie, and inf <= inf holds: two equal infinities are "A wins", as in numpy.  Bytes (:225-228 through
+ * save_img, :40): A wins (239, 138, 98), tie (247, 247, 247), B wins (103, 169, 207), neither (0, 0, 0).  Each coloured map lies in the
+ * top-left corner of an H x W panel of 255 (:230 np.ones — not rnerf_errmap_sheet's black panels), and 5 columns of 255 follow every
+ * panel, the last included (:234).  compare.py's {name}_NNN.png are slices of this frame; the text labels of :232 are not drawn.
+ * counts (nullable): device int64[K][4], 8-byte aligned, counts[k] = {A wins, tie, B wins, neither} over the map_h[k] x map_w[k]
+ * elements of map k; the four add up to that element count.  The call clears it on `stream`; integer arithmetic only (per-wave
+ * sums, LDS and global integer atomics), so the same inputs give the same numbers on every run.  One memset and one launch.
+ * RNERF_ERR_ARG before any device work for null pointers, K outside [1, 4], H or W < 1, a map that is empty or larger than the image,
+ * a frame of 2^31 bytes or more, a misaligned counts, an `out` or `counts` that overlaps a map or the other. */
+int rnerf_compare_sheet(int32_t H, int32_t W, int32_t K, const float* const* maps_a, const float* const* maps_b, const int32_t* map_h,
+                        const int32_t* map_w, uint8_t* out, int64_t* counts, void* stream);
+
+/* rnerf_compare_strip: one frame of export.py:92-133 as bytes, one launch.  images: HOST array of 1 <= N <= 4 device uint8[H][W][3];
+ * reference: device uint8[H][W][3]; out: device uint8[H][N (W + 5) + W][3].  Columns (:126-133): image 0, 5 of 255, ..., image N-1,
+ * 5 of 255, the reference; no gap after the reference.  (rx, ry, rw, rh): the highlight rectangle of :93 (cv2.boundingRect's x, y, w,
+ * h); rw == 0 or rh == 0: none.  With one, a byte v of an image outside it becomes (:102-108)
+ *   trunc(clip(((v / 255.0) * 0.5 + 1.0 * 0.5) * 255.0, 0, 255))   in double
+ * through a 256-entry table made on the host from that expression (not (v + 255) / 2: v = 73 gives 163, v = 105 gives 179); inside,
+ * the same expression at weight 1 is the identity on every byte.  The reference is copied as it is: export.py fades only the
+ * predictions.  The text labels of :111-115 are not drawn and the channel order is the caller's (the [..., ::-1] of :133 undoes
+ * cv2.imread's BGR).  RNERF_ERR_ARG before any device work for null pointers, N outside [1, 4], H or W < 1, a rectangle that does not
+ * lie inside the image, a strip of 2^31 bytes or more, an `out` that overlaps an input. */
+int rnerf_compare_strip(const uint8_t* const* images, int32_t N, const uint8_t* reference, int32_t H, int32_t W, int32_t rx, int32_t ry,
+                        int32_t rw, int32_t rh, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

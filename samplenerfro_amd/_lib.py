@@ -200,6 +200,9 @@ SIGNATURES = {
     "rnerf_components_label": (C.c_int, [_vp, C.POINTER(_i32 * 3), _i32, _i32, _vp, _vp, _vp]),
     "rnerf_components_stats": (C.c_int, [_vp, C.POINTER(_i32 * 3), _vp, _vp, _vp, _vp]),
     "rnerf_components_apply": (C.c_int, [_vp, _vp, _dbl, _vp, _vp, _dbl, _vp, _i32, C.POINTER(_i32 * 3), _vp]),
+    # A/B comparison of two runs: metric/compare.py, metric/export.py (csrc/errmap.hip)
+    "rnerf_compare_sheet": (C.c_int, [_i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), _vp, _vp, _vp]),
+    "rnerf_compare_strip": (C.c_int, [C.POINTER(_vp), _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -871,6 +871,66 @@ def errmap_sheet(reference: torch.Tensor, test: torch.Tensor, maps) -> torch.Ten
     return out
 
 
+def compare_sheet(maps_a, maps_b, H: int, W: int, *, counts: bool = True):
+    """The win/loss frame of metric/compare.py:216-236 as bytes (rnerf_compare_sheet).  maps_a, maps_b: the same number (1 to 4) of
+    float32 device tensors [h_k, w_k], h_k <= H, w_k <= W, the k-th error map of run A and of run B.  -> (uint8 [H, K (W + 5), 3]: per
+    map an H x W panel of 255 with the map's pixels coloured by the run with the lower error, 5 columns of 255 after every panel; int64
+    [K, 4] = {A wins, tie, B wins, neither} per map, or None without counts).  One memset and one launch on the current stream of the
+    maps' device; nothing is synchronised."""
+    maps_a, maps_b = list(maps_a), list(maps_b)
+    if len(maps_a) != len(maps_b) or not maps_a:
+        raise ValueError(f"compare_sheet: need as many maps of run A as of run B and at least one, got {len(maps_a)} and {len(maps_b)}")
+    dev = maps_a[0].device
+    ms = []
+    for k, (a, b) in enumerate(zip(maps_a, maps_b)):
+        if a.dim() != 2 or tuple(a.shape) != tuple(b.shape) or a.device != dev or b.device != dev:
+            raise ValueError(f"compare_sheet: map {k} must be two [h, w] tensors of one shape on {dev}, got {tuple(a.shape)} on {a.device} and "
+                             f"{tuple(b.shape)} on {b.device}")
+        ms.append((_chk(a, f"map {k} of run A"), _chk(b, f"map {k} of run B")))
+    K, H, W = len(ms), int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"compare_sheet: need H >= 1 and W >= 1, got {H} x {W}")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        out = torch.empty((H, K * (W + 5), 3), dtype=torch.uint8, device=dev)
+        cnt = torch.empty((K, 4), dtype=torch.int64, device=dev) if counts else None
+        pa = (C.c_void_p * K)(*[a.data_ptr() for a, _ in ms])
+        pb = (C.c_void_p * K)(*[b.data_ptr() for _, b in ms])
+        hs = (C.c_int32 * K)(*[int(a.shape[0]) for a, _ in ms])
+        wds = (C.c_int32 * K)(*[int(a.shape[1]) for a, _ in ms])
+        check(lib.rnerf_compare_sheet(H, W, K, pa, pb, hs, wds, ptr(out), ptr(cnt), torch.cuda.current_stream(dev).cuda_stream),
+              "rnerf_compare_sheet")
+    return out, cnt
+
+
+def compare_strip(images, reference: torch.Tensor, rect=None) -> torch.Tensor:
+    """One frame of metric/export.py:92-133 as bytes (rnerf_compare_strip).  images: 1 to 4 uint8 device tensors [H, W, 3]; reference:
+    uint8 [H, W, 3]; rect: None or (x, y, w, h) inside the image (cv2.boundingRect's order; w == 0 or h == 0: none).  -> uint8
+    [H, N (W + 5) + W, 3]: the images, 5 columns of 255 after each, then the reference; with a rectangle the images are faded towards
+    white outside it (export.py:102-108), the reference is not.  One launch on the current stream; nothing is synchronised."""
+    images = list(images)
+    r = _chk(reference, "reference", torch.uint8)
+    if r.dim() != 3 or int(r.shape[2]) != 3 or int(r.shape[0]) < 1 or int(r.shape[1]) < 1:
+        raise ValueError(f"compare_strip: need a non-empty [H, W, 3] reference, got {tuple(reference.shape)}")
+    if not images:
+        raise ValueError("compare_strip: need at least one image")
+    dev = r.device
+    ims = []
+    for i, im in enumerate(images):
+        if tuple(im.shape) != tuple(r.shape) or im.device != dev:
+            raise ValueError(f"compare_strip: image {i} must be {tuple(r.shape)} on {dev} like the reference, got {tuple(im.shape)} on {im.device}")
+        ims.append(_chk(im, f"image {i}", torch.uint8))
+    N, H, W = len(ims), int(r.shape[0]), int(r.shape[1])
+    rx, ry, rw, rh = (0, 0, 0, 0) if rect is None else (int(v) for v in rect)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        out = torch.empty((H, N * (W + 5) + W, 3), dtype=torch.uint8, device=dev)
+        ptrs = (C.c_void_p * N)(*[im.data_ptr() for im in ims])
+        check(lib.rnerf_compare_strip(ptrs, N, ptr(r), H, W, rx, ry, rw, rh, ptr(out), torch.cuda.current_stream(dev).cuda_stream),
+              "rnerf_compare_strip")
+    return out
+
+
 def _vis_plane(t, name: str) -> torch.Tensor:
     if t.dim() != 2 or int(t.shape[0]) < 1 or int(t.shape[1]) < 1:
         raise ValueError(f"{name}: need a non-empty [H, W] plane, got shape {tuple(t.shape)}")
