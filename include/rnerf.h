@@ -901,6 +901,47 @@ int rnerf_compare_sheet(int32_t H, int32_t W, int32_t K, const float* const* map
 int rnerf_compare_strip(const uint8_t* const* images, int32_t N, const uint8_t* reference, int32_t H, int32_t W, int32_t rx, int32_t ry,
                         int32_t rw, int32_t rh, uint8_t* out, void* stream);
 
+/* ---- Bent-path diagnostics: refraction maps and path plots (csrc/paths.hip).  Appended; RNERF_VERSION stays 4 -------------------------
+ * Records are float4 [num_nodes][B] as rnerf_march / rnerf_march_all write them: path_pd = (x, y, z, dist), path_dr = (dx, dy, dz, 0)
+ * normalised, path_ior = (n, dn/dx, dn/dy, dn/dz).  All pointers are device pointers unless marked HOST.
+ *
+ * rnerf_path_summary: the per-pixel map eval.py:173,195 carries commented out (`pred_mask = any(|idx_grad| > 1e-3 along the path)`,
+ * mask_{idx}.png) and what extract_mesh.py:178-223 reads off the pickled path of one pixel, for every ray at once.  Arithmetic is
+ * individually rounded float32 unless stated, sqrt correctly rounded, sums of squares taken as (a a + b b) + c c.  Node k of ray r is
+ * refracting when sqrt(sumsq(ior[k].yzw)) > (float)grad_eps: strict, and a NaN norm is not refracting (the reference's threshold is 1e-3,
+ * eikonal_utils.py:35).  nodes int32[3][B]: [0] the count of refracting nodes, [1] the first such k, [2] the last, both -1 if none.
+ * maps float[2][B]: [0] bend = sqrt(sumsq(dr[N-1].xyz - dr[0].xyz)) = 2 sin(theta / 2) of the total deflection theta; [1] optical =
+ * (float) sum_{k=0}^{N-2} (double)(ior[k].x - 1.0f) (double)len_k with len_k = sqrt(sumsq(pd[k].xyz - pd[k+1].xyz)), the sum and the
+ * products in float64, one term after the other in ascending k: the optical thickness of what the ray crossed beyond vacuum.  One launch,
+ * one ray per lane, no atomics; every record of path_pd and path_ior is read once.  RNERF_ERR_ARG before any device work for null
+ * pointers, num_nodes or B < 1, a NaN grad_eps, records not 16-byte aligned. */
+int rnerf_path_summary(const float* path_pd, const float* path_dr, const float* path_ior, int32_t num_nodes, int32_t B, double grad_eps,
+                       int32_t* nodes, float* maps, void* stream);
+
+/* rnerf_path_plot: plt_utils.plot_path (called at extract_mesh.py:225; its four views :86) as finished bytes, without matplotlib: the
+ * polylines of R selected rays in P orthographic panels.  rays int32[R]: ray indices into [0, B) (one outside is skipped); ray_rgb
+ * uint8[R][3]; panels HOST double[P][2][4], 1 <= P <= 8; 1 <= size <= 8192; box HOST double[6] = (min x, y, z, max x, y, z), null: none;
+ * floor_z: the plane of the shadow (:54), NaN: none; path_ior null: no markers; out uint8[P][size][size][3]; workspace:
+ * rnerf_path_plot_workspace_bytes(P, size) bytes, 4-byte aligned.  The text, the axes and matplotlib's perspective are not reproduced.
+ *   Pixel of a point: u = ((m00 x + m01 y) + m02 z) + m03 in float64 with every operation rounded, v from row 1 in the same way; column
+ *   floor(u), row floor(v).  A point whose u or v is not finite or has |.| >= 2^30 cannot be drawn: its marker and the segments that
+ *   touch it are skipped.
+ *   Segment between the pixels (x0, y0) and (x0 + dx, y0 + dy): n = max(|dx|, |dy|); pixel i of n + 1 is (x0 + floor((2 i dx + n) / (2 n)),
+ *   y0 + floor((2 i dy + n) / (2 n))) in int64, floor division; n = 0 is one pixel.  Only the i whose major coordinate lies inside the
+ *   panel are visited, so a segment costs at most `size` iterations whatever its length.
+ *   Drawn: the 12 box edges (edge e runs along axis e / 4 from min to max; bits 0 and 1 of e choose max on axes (e / 4 + 1) % 3 and
+ *   (e / 4 + 2) % 3); per ray the segments node k -> k + 1, the same segments with z replaced by floor_z, and a 3 x 3 marker on every
+ *   refracting node (the rule of rnerf_path_summary).  Every covered pixel inside the panel does atomicMax(key, layer << 28 | id), layers
+ *   1 box, 2 shadow, 3 path, 4 marker, id = the slot j of the ray in `rays` or the edge number: an integer maximum does not depend on
+ *   the order, so the bytes are the same on every run.  Colours: key 0 (255, 255, 255), box (255, 0, 0), shadow (139, 206, 151) (:55),
+ *   path ray_rgb[j], marker (0, 0, 0).
+ * One memset and two launches.  RNERF_ERR_ARG before any device work for null pointers, P or size out of range (the workspace query then
+ * returns 0 with the message), R < 0 or >= 2^28, num_nodes or B < 1 with R > 0, a NaN grad_eps, misaligned pointers. */
+size_t rnerf_path_plot_workspace_bytes(int32_t P, int32_t size);
+int rnerf_path_plot(const float* path_pd, const float* path_ior, int32_t num_nodes, int32_t B, const int32_t* rays, const uint8_t* ray_rgb,
+                    int32_t R, const double* panels /* HOST [P][2][4] */, int32_t P, int32_t size, const double* box /* HOST [6] */,
+                    double floor_z, double grad_eps, void* workspace, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,10 @@ SIGNATURES = {
     # A/B comparison of two runs: metric/compare.py, metric/export.py (csrc/errmap.hip)
     "rnerf_compare_sheet": (C.c_int, [_i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), _vp, _vp, _vp]),
     "rnerf_compare_strip": (C.c_int, [C.POINTER(_vp), _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    # bent-path diagnostics: refraction maps and path plots (csrc/paths.hip)
+    "rnerf_path_summary": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _dbl, _vp, _vp, _vp]),
+    "rnerf_path_plot_workspace_bytes": (C.c_size_t, [_i32, _i32]),
+    "rnerf_path_plot": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, C.POINTER(_dbl), _i32, _i32, C.POINTER(_dbl), _dbl, _dbl, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -11,6 +11,8 @@ With errmap=True every view also gets metric/summary.py's error maps, comparison
 rnerf_errmap_mse, rnerf_ssim_summary, rnerf_flip, rnerf_errmap_sheet), scored on the 8-bit prediction as summary.py scores the PNG.
 With lpips=weights (lpips.load_weights) each view is also scored with LPIPS (utils.compute_lpips, rnerf_lpips; summary.py:63-68), and
 errmap=True then carries the LPIPS map and column as well.
+With path_maps=True every view also gets the refraction maps eval.py:173,195 carries commented out (paths.view_maps: the march again with
+its IoR record, reduced per ray by rnerf_path_summary), written with save_output.
 """
 from __future__ import annotations
 
@@ -102,7 +104,7 @@ def apply_mask(pred_color: torch.Tensor, pixels: torch.Tensor, mask, mask_mode: 
 def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192, normalize_disp: bool = False, out_dir: Optional[str] = None,
              step=None, save_output: bool = False, render_path: bool = False, flip: bool = False,
              flip_pixels_per_degree: Optional[float] = None, masks=None, mask_mode: Optional[str] = None, vis_suite: bool = False,
-             errmap: bool = False, lpips=None) -> dict:
+             errmap: bool = False, lpips=None, path_maps: bool = False) -> dict:
     """Render and score every view (eval.py:155-215).
 
     model / variables: what models.construct_nerf returns; views: batches as device_views yields them; rng: the render key (eval.py passes
@@ -144,7 +146,13 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
     on the 8-bit prediction like the rest of the summary: "summary" gains "lpips_values" and "lpips", the clipped map (summary.py:67)
     enters the sheet as the third of four maps (errmap.MAP_NAMES_LPIPS; the sheet is (2 + 4)(W + 5) wide), write_error_maps also writes
     lpips_{idx:03d}.png, and metric_list / result carry the LPIPS column.  A view or crop below 31 x 31 is a ValueError.  With
-    lpips=None the keys, the files and the launches are those of the loop without it."""
+    lpips=None the keys, the files and the launches are those of the loop without it.
+
+    path_maps=True: paths.view_maps for every view (the view is marched once more, `chunk` rays at a time, with the IoR record; no MLP):
+    the result gains "refracted", per view the fraction of rays with a node where |grad n| > 1e-3 (eval.py:173's pred_mask), from an
+    integer count read back once per view.  With save_output it also writes mask_{idx:03d}.png (the name at eval.py:195),
+    bend_{idx:03d}.png and optical_{idx:03d}.png (paths.visualize_maps through utils.save_img).  Works with render_path as well.  With
+    path_maps=False the keys, the files and the launches are those of the loop without it."""
     if errmap and render_path:
         raise ValueError("evaluate: errmap needs ground truth, render_path has none")
     if errmap:
@@ -162,6 +170,7 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
         return model.apply(variables, key_0, key_1, rays, False, path=path)
 
     psnr_values, ssim_values, flip_values, lpips_values = [], [], [], []
+    refracted_values = []
     map_names = ()
     if errmap:
         map_names = em.MAP_NAMES_LPIPS if lpips is not None else em.MAP_NAMES
@@ -220,6 +229,13 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
             if save_output:
                 for name in ("depth", "depth_mod", "depth_normals"):
                     utils.save_img(suite[name], os.path.join(out_dir, "{}_{:03d}.png".format(name, idx)))
+        if path_maps:
+            from . import paths
+            pmaps = paths.view_maps(model, variables, batch["rays"], chunk=chunk)
+            refracted_values.append(int(pmaps["refracted"].sum()) / pmaps["refracted"].numel())
+            if save_output:
+                for name, img in paths.visualize_maps(pmaps).items():
+                    utils.save_img(img, os.path.join(out_dir, "{}_{:03d}.png".format(name, idx)))
     if num_rays:
         torch.cuda.synchronize(pred_color.device)
     seconds = time.perf_counter() - t0
@@ -242,6 +258,8 @@ def evaluate(model, variables, views: Iterable[dict], rng, *, chunk: int = 8192,
         res["lpips"] = float(np.mean(np.array(lpips_values))) if lpips_values else None
     if mask_mode is not None:
         res["mask_mode"] = mask_mode
+    if path_maps:
+        res["refracted"] = refracted_values
     if errmap:
         mean = lambda v: float(np.mean(np.array(v))) if v else None
         res["summary"] = {"psnrs": summary_values["psnr"], "ssims": summary_values["ssim"], "flips": summary_values["flip"],

@@ -1012,3 +1012,68 @@ def images_prepare(u8: torch.Tensor, factor: int = 1, white_bkgd: bool = False, 
     check(lib.rnerf_images_prepare(ptr(src), n, H, W, ch, factor, int(bool(white_bkgd)), ptr(out), torch.cuda.current_stream(src.device).cuda_stream),
           "rnerf_images_prepare")
     return out
+
+
+def _path_records(what: str, pd, dr=None, ior=None):
+    """The march records as contiguous float32 [N, B, 4] tensors of one shape on one device (None stays None) -> (pd, dr, ior, N, B)."""
+    if pd.dim() != 3 or int(pd.shape[2]) != 4 or int(pd.shape[0]) < 1 or int(pd.shape[1]) < 1:
+        raise ValueError(f"{what}: path_pd must be a non-empty [num_nodes, B, 4] tensor, got {tuple(pd.shape)}")
+    out = [_chk(pd, "path_pd")]
+    for t, name in ((dr, "path_dr"), (ior, "path_ior")):
+        if t is not None and (tuple(t.shape) != tuple(pd.shape) or t.device != pd.device):
+            raise ValueError(f"{what}: {name} {tuple(t.shape)} on {t.device} does not match path_pd {tuple(pd.shape)} on {pd.device}")
+        out.append(None if t is None else _chk(t, name))
+    return out[0], out[1], out[2], int(pd.shape[0]), int(pd.shape[1])
+
+
+def path_summary(path_pd: torch.Tensor, path_dr: torch.Tensor, path_ior: torch.Tensor, grad_eps: float = 1e-3):
+    """rnerf_path_summary: the march records [N, B, 4] reduced per ray -> (nodes int32 [3, B] = the count of refracting nodes
+    (|grad n| > grad_eps), the first and the last of them (-1: none); maps float32 [2, B] = bend (the length of the difference of the
+    last and the first direction) and optical (sum of (n - 1) x segment length, accumulated in float64 in node order)).  One launch on
+    the current stream of the records' device; nothing is synchronised."""
+    pd, dr, ior, N, B = _path_records("path_summary", path_pd, path_dr, path_ior)
+    if dr is None or ior is None:
+        raise ValueError("path_summary: needs path_dr and path_ior (march with want_ior=True)")
+    lib = _lib.load()
+    dev = pd.device
+    with torch.cuda.device(dev):
+        nodes = torch.empty((3, B), dtype=torch.int32, device=dev)
+        maps = torch.empty((2, B), dtype=torch.float32, device=dev)
+        check(lib.rnerf_path_summary(ptr(pd), ptr(dr), ptr(ior), N, B, float(grad_eps), ptr(nodes), ptr(maps),
+                                     torch.cuda.current_stream(dev).cuda_stream), "rnerf_path_summary")
+    return nodes, maps
+
+
+def path_plot(path_pd: torch.Tensor, path_ior: Optional[torch.Tensor], rays: torch.Tensor, ray_rgb: torch.Tensor, panels, size: int, *,
+              box=None, floor_z: float = float("nan"), grad_eps: float = 1e-3) -> torch.Tensor:
+    """rnerf_path_plot: the polylines of the rays `rays` (int32 [R], indices into B) of path_pd [N, B, 4] in P orthographic panels ->
+    uint8 [P, size, size, 3].  ray_rgb: uint8 [R, 3]; panels: float64 [P, 2, 4] on the host (paths.view_matrices); box: None or (min x, y,
+    z, max x, y, z), drawn as 12 red edges; floor_z: the plane of the shadow polyline (NaN: none); path_ior [N, B, 4] (None: none): a
+    3 x 3 black marker on every node with |grad n| > grad_eps.  One memset and two launches on the current stream; nothing is
+    synchronised, the ray indices are not read back (one outside [0, B) is skipped by the kernel)."""
+    import numpy as np
+    pd, _, ior, N, B = _path_records("path_plot", path_pd, None, path_ior)
+    dev = pd.device
+    r = _chk(rays, "rays", torch.int32)
+    c = _chk(ray_rgb, "ray_rgb", torch.uint8)
+    R = int(r.numel())
+    if r.dim() != 1 or tuple(c.shape) != (R, 3) or r.device != dev or c.device != dev:
+        raise ValueError(f"path_plot: need rays [R] and ray_rgb [R, 3] on {dev}, got {tuple(r.shape)} on {r.device} and {tuple(c.shape)} on {c.device}")
+    pan = np.ascontiguousarray(np.asarray(panels, dtype=np.float64))
+    if pan.ndim != 3 or pan.shape[1:] != (2, 4) or pan.shape[0] < 1:
+        raise ValueError(f"path_plot: panels must be [P, 2, 4], got {pan.shape}")
+    P, size = int(pan.shape[0]), int(size)
+    bx = None
+    if box is not None:
+        bx = np.ascontiguousarray(np.asarray(box, dtype=np.float64).reshape(-1))
+        if bx.shape != (6,):
+            raise ValueError("path_plot: box must be (min x, y, z, max x, y, z)")
+    lib = _lib.load()
+    dp = C.POINTER(C.c_double)
+    with torch.cuda.device(dev):
+        ws = workspace("rnerf_path_plot_workspace_bytes", P, size, device=dev)
+        out = torch.empty((P, size, size, 3), dtype=torch.uint8, device=dev)
+        check(lib.rnerf_path_plot(ptr(pd), ptr(ior), N, B, ptr(r), ptr(c), R, pan.ctypes.data_as(dp), P, size,
+                                  bx.ctypes.data_as(dp) if bx is not None else None, float(floor_z), float(grad_eps), ptr(ws), ptr(out),
+                                  torch.cuda.current_stream(dev).cuda_stream), "rnerf_path_plot")
+    return out
