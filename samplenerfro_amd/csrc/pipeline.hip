@@ -339,13 +339,14 @@ struct Carver {
 struct FwdBuffers {
   float *path_pd, *path_dr, *bk_dirs, *bkgd, *raw_c, *weights, *u, *rows_pd, *rows_dr, *scratch, *raw_f, *tmp_level, *tmp_level2;
 };
-static size_t carve_forward(const rnerf_model* m, int32_t B, bool own_path, void* ws, FwdBuffers* f) {
-  Carver c(ws);
+// The forward part of a workspace, for rnerf_forward (M = 0) and for the train step, whose background rows are widened to B + M:
+// rows [0,B) of bk_dirs / bkgd belong to the rays, rows [B,B+M) to the env-map patch.  -> the bytes carved so far, rounded up.
+static size_t carve_forward(Carver& c, const rnerf_model* m, int32_t B, size_t M, bool own_path, FwdBuffers* f) {
   const size_t Nc = m->num_coarse, Nf = m->num_fine, N = Nc * (size_t)m->num_path, S = Nc + Nf;
   f->path_pd = own_path ? c.take<float>(N * B * 4) : nullptr;
   f->path_dr = own_path ? c.take<float>(N * B * 4) : nullptr;
-  f->bk_dirs = c.take<float>((size_t)B * 4);
-  f->bkgd = c.take<float>((size_t)B * 3);
+  f->bk_dirs = c.take<float>((B + M) * 4);
+  f->bkgd = c.take<float>((B + M) * 3);
   f->raw_c = c.take<float>(Nc * B * 4);
   f->weights = c.take<float>(Nc * B);
   f->u = f->rows_pd = f->rows_dr = f->scratch = f->raw_f = f->tmp_level = f->tmp_level2 = nullptr;
@@ -372,19 +373,37 @@ static int check_model(const rnerf_model* m, int32_t B, const char* who) {
 // rnerf_model.bd_cut: 0 = none, 1 = the bd_cut_dist pair on the fine level (rnerf/models.py:479-524), 2 = use_mask_bbox (:261-271,398-408):
 // density only at samples inside rnerf_model.bd_cut_bbox (the host puts the grid's nmin / nmax there), in BOTH levels' renderings
 static inline int level_mask_mode(const rnerf_model* m) { return m->bd_cut == 2 ? 3 : 0; }
-static inline const double* level_mask_box(const rnerf_model* m) { return m->bd_cut == 2 ? m->bd_cut_bbox : nullptr; }
 struct Level { float *rgb, *dist, *acc, *trans, *tb; };
 static Level level_of(float* out, int32_t B) { return Level{out, out + 3 * (size_t)B, out + 4 * (size_t)B, out + 5 * (size_t)B, out + 6 * (size_t)B}; }
 
+// What the compositing reads of one level: the MLP's raw output and its rows (coarse: the path through the jitter, S = Nc; fine: the resampled rows, S = Nc + Nf)
+struct LevelRows { const float *raw, *rows_pd, *rows_dr; const int32_t* node_of_sample; int32_t S; };
+
+// rnerf_composite of one level into `out` (weights: the resampler's input, or nullptr).  mask_mode: rnerf_composite's, by default the
+// level's own rendering (level_mask_mode); the box of every masked mode is rnerf_model.bd_cut_bbox.
+static int composite_level(const rnerf_model* m, int32_t B, const LevelRows& l, const float* bkgd, Level out, float* weights, void* stream, int mask_mode = -1) {
+  if (mask_mode < 0) mask_mode = level_mask_mode(m);
+  return rnerf_composite(l.raw, l.rows_pd, l.rows_dr, l.node_of_sample, l.S, B, bkgd, m->white_bkgd, m->rgb_padding, m->sigma_bias, out.rgb, out.dist, out.acc,
+                         out.trans, out.tb, weights, nullptr, mask_mode, mask_mode ? m->bd_cut_bbox : nullptr, stream);
+}
+
+// The loss side of rnerf_composite_backward.  The LAST level carries the data term and the background term (its trans / tb, the loss sums,
+// bg_weight) and is the first writer of d_bkgd; the coarse level under a fine one has the plain mse term only and accumulates on top of it.
+struct LevelLoss { const float *pixels, *trans, *tb, *sums; double mse_scale, bg_weight; int accumulate_bkgd; };
+static int composite_level_backward(const rnerf_model* m, int32_t B, const LevelRows& l, const float* bkgd, const float* rgb, const LevelLoss& loss, float* d_raw,
+                                    float* d_bkgd, int mask_mode, void* stream) {
+  return rnerf_composite_backward(l.raw, l.rows_pd, l.rows_dr, l.node_of_sample, l.S, B, bkgd, m->rgb_padding, m->sigma_bias, rgb, loss.pixels, loss.trans, loss.tb,
+                                  loss.sums, loss.mse_scale, loss.bg_weight, d_raw, d_bkgd, loss.accumulate_bkgd, m->white_bkgd, mask_mode,
+                                  mask_mode ? m->bd_cut_bbox : nullptr, stream);
+}
+
 // the bd_cut_dist pair of rnerf/models.py:479-524 on the fine level: trans <- mask-mode-1 transmittance, tb <- trans * (mask-mode-2 colour)
-static int bd_cut_pair(const rnerf_model* m, const float* raw_f, const float* rows_pd, const float* rows_dr, int32_t S, int32_t B, const float* bkgd,
-                       Level out, float* tmp1, float* tmp2, void* stream) {
+static int bd_cut_pair(const rnerf_model* m, const LevelRows& fine, int32_t B, const float* bkgd, Level out, float* tmp1, float* tmp2, void* stream) {
   Level a = level_of(tmp1, B), b = level_of(tmp2, B);
-  int rc = rnerf_composite(raw_f, rows_pd, rows_dr, nullptr, S, B, nullptr, m->white_bkgd, m->rgb_padding, m->sigma_bias, a.rgb, a.dist, a.acc, out.trans,
-                           a.tb, nullptr, nullptr, 1, m->bd_cut_bbox, stream);
+  a.trans = out.trans;
+  int rc = composite_level(m, B, fine, nullptr, a, nullptr, stream, 1);
   if (rc) return rc;
-  rc = rnerf_composite(raw_f, rows_pd, rows_dr, nullptr, S, B, bkgd, m->white_bkgd, m->rgb_padding, m->sigma_bias, b.rgb, b.dist, b.acc, b.trans, b.tb, nullptr,
-                       nullptr, 2, m->bd_cut_bbox, stream);
+  rc = composite_level(m, B, fine, bkgd, b, nullptr, stream, 2);
   if (rc) return rc;
   hipLaunchKernelGGL(bd_cut_mul_kernel, dim3((3 * B + 255) / 256), dim3(256), 0, (hipStream_t)stream, out.trans, b.rgb, B, out.tb);
   RNERF_CHECK_LAUNCH();
@@ -444,7 +463,8 @@ extern "C" int rnerf_stratified_u_dev(const uint32_t* key_dev, int32_t B, int32_
 extern "C" size_t rnerf_forward_workspace_bytes(const rnerf_model* m, int32_t B) {
   if (!m || B < 1) return 0;
   FwdBuffers f;
-  return carve_forward(m, B, true, nullptr, &f);
+  Carver c(nullptr);
+  return carve_forward(c, m, B, 0, true, &f);
 }
 
 extern "C" int rnerf_forward(const rnerf_model* m, const float* origins, const float* viewdirs, int32_t B, const int32_t* jitter, const float* u_fine,
@@ -459,7 +479,8 @@ extern "C" int rnerf_forward(const rnerf_model* m, const float* origins, const f
   RNERF_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "rnerf_forward: workspace must be 256-byte aligned");
   const int32_t Nc = m->num_coarse, Nf = m->num_fine, N = Nc * m->num_path, S = Nc + Nf;
   FwdBuffers f;
-  carve_forward(m, B, path_pd == nullptr, workspace, &f);
+  Carver carver(workspace);
+  carve_forward(carver, m, B, 0, path_pd == nullptr, &f);
   if (!path_pd) {
     RNERF_TRY(rnerf_march(m->table, &m->grid, origins, viewdirs, B, m->near, m->far, N, f.path_pd, f.path_dr, nullptr, nullptr, stream));
     path_pd = f.path_pd; path_dr = f.path_dr;
@@ -469,16 +490,14 @@ extern "C" int rnerf_forward(const rnerf_model* m, const float* origins, const f
   RNERF_CHECK_LAUNCH();
   RNERF_TRY(rnerf_bkgd_forward(m->bkgd_params, f.bk_dirs, 4, B, m->rgb_padding, f.bkgd, stream));
   RNERF_TRY(rnerf_nerfmlp_forward(m->packed_coarse, m->precision, path_pd, path_dr, jitter, Nc, B, f.raw_c, max_workgroups, stream));
-  Level c = level_of(out_coarse, B);
-  RNERF_TRY(rnerf_composite(f.raw_c, path_pd, path_dr, jitter, Nc, B, f.bkgd, m->white_bkgd, m->rgb_padding, m->sigma_bias, c.rgb, c.dist, c.acc, c.trans, c.tb,
-                            Nf > 0 ? f.weights : nullptr, nullptr, level_mask_mode(m), level_mask_box(m), stream));
+  const LevelRows coarse{f.raw_c, path_pd, path_dr, jitter, Nc}, fine{f.raw_f, f.rows_pd, f.rows_dr, nullptr, S};
+  RNERF_TRY(composite_level(m, B, coarse, f.bkgd, level_of(out_coarse, B), Nf > 0 ? f.weights : nullptr, stream));
   if (Nf > 0) {
     RNERF_TRY(rnerf_resample(path_pd, path_dr, N, B, jitter, Nc, f.weights, u_fine, u_per_ray, Nf, f.rows_pd, f.rows_dr, nullptr, f.scratch, stream));
     RNERF_TRY(rnerf_nerfmlp_forward(m->packed_fine, m->precision, f.rows_pd, f.rows_dr, nullptr, S, B, f.raw_f, max_workgroups, stream));
     Level o = level_of(out_fine, B);
-    RNERF_TRY(rnerf_composite(f.raw_f, f.rows_pd, f.rows_dr, nullptr, S, B, f.bkgd, m->white_bkgd, m->rgb_padding, m->sigma_bias, o.rgb, o.dist, o.acc, o.trans,
-                              o.tb, nullptr, nullptr, level_mask_mode(m), level_mask_box(m), stream));
-    if (m->bd_cut == 1) RNERF_TRY(bd_cut_pair(m, f.raw_f, f.rows_pd, f.rows_dr, S, B, f.bkgd, o, f.tmp_level, f.tmp_level2, stream));
+    RNERF_TRY(composite_level(m, B, fine, f.bkgd, o, nullptr, stream));
+    if (m->bd_cut == 1) RNERF_TRY(bd_cut_pair(m, fine, B, f.bkgd, o, f.tmp_level, f.tmp_level2, stream));
   }
   return RNERF_OK;
 }
@@ -503,26 +522,9 @@ struct TrainBuffers {
 static size_t carve_train(const rnerf_model* m, const rnerf_train_cfg* c, int32_t B, bool own_path, void* ws, TrainBuffers* t) {
   const size_t Nc = m->num_coarse, Nf = m->num_fine, S = Nc + Nf;
   const size_t M = c->bg_smooth_weight > 0 ? (size_t)c->bg_patch_size * c->bg_patch_size : 0;
-  // the forward part: as carve_forward, with the background rows widened to B + M
   Carver k(ws);
-  const size_t N = Nc * (size_t)m->num_path;
-  FwdBuffers& f = t->f;
-  f.path_pd = own_path ? k.take<float>(N * B * 4) : nullptr;
-  f.path_dr = own_path ? k.take<float>(N * B * 4) : nullptr;
-  f.bk_dirs = k.take<float>((B + M) * 4);
-  t->out_all = k.take<float>((B + M) * 3);           // rows [0,B): bkgd of the rays, [B,B+M): rgb of the env patch
-  f.bkgd = t->out_all;
-  f.raw_c = k.take<float>(Nc * B * 4);
-  f.weights = k.take<float>(Nc * B);
-  f.u = f.rows_pd = f.rows_dr = f.scratch = f.raw_f = f.tmp_level = f.tmp_level2 = nullptr;
-  if (Nf > 0) {
-    f.u = k.take<float>(Nf * (size_t)B);
-    f.rows_pd = k.take<float>(S * B * 4);
-    f.rows_dr = k.take<float>(S * B * 4);
-    f.scratch = k.take<float>(S * B);
-    f.raw_f = k.take<float>(S * B * 4);
-    if (m->bd_cut) { f.tmp_level = k.take<float>((size_t)RNERF_LEVEL_FLOATS * B); f.tmp_level2 = k.take<float>((size_t)RNERF_LEVEL_FLOATS * B); }
-  }
+  carve_forward(k, m, B, M, own_path, &t->f);
+  t->out_all = t->f.bkgd;                            // rows [0,B): bkgd of the rays, [B,B+M): rgb of the env patch
   t->jitter = k.take<int32_t>(Nc);
   t->key_u = k.take<uint32_t>(4);
   t->packed_c = k.bytes(rnerf_nerfmlp_packed_bytes(RNERF_PREC_F16X3));
@@ -601,7 +603,6 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
   //      follow on the aux stream while the coarse forward runs and are joined before the fine forward / the backward.
   //      (Round 4: before, the coarse forward waited for five launches — three 16-byte memsets among them — and started at +88 us.)
   void* aux = c->aux_stream;
-  bool pre_zeroed = false;      // the head of the step has cleared the accumulator words of its kernels (aux stream only)
   struct Mark { hipEvent_t e = nullptr; ~Mark() { if (e) pool_put(e); } } fine_packed;      // (an early error return must not leak it)
   if (aux) {
     RNERF_TRY(rnerf_fork(stream, aux));
@@ -612,7 +613,6 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
     void* dys[2] = {t.dy, t.dy_c};
     const int64_t dy_rows[2] = {(int64_t)(Nf > 0 ? S : Nc) * B, (int64_t)Nc * B};
     RNERF_TRY(nerfmlp_step_zero(prec, streams, Nf > 0 ? 2 : 1, bwd, dys, dy_rows, t.dy_c ? 2 : 1, (hipStream_t)aux));
-    pre_zeroed = true;
     RNERF_TRY(nerfmlp_pack_impl(th_c, prec, t.packed_c, false, (hipStream_t)aux, false));
   }
   // ---- forward (models.forward with ctx) ----
@@ -647,9 +647,9 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
     RNERF_TRY(rnerf_nerfmlp_pack(th_c, prec, t.packed_c, stream));
   }
   RNERF_TRY(rnerf_nerfmlp_forward_train(t.packed_c, prec, path_pd, path_dr, jitter, Nc, B, f.raw_c, t.save_c, bwd, max_workgroups, stream));
+  const LevelRows coarse{f.raw_c, path_pd, path_dr, jitter, Nc}, fine{f.raw_f, f.rows_pd, f.rows_dr, nullptr, S};
   Level lc = level_of(t.level_c, B);
-  RNERF_TRY(rnerf_composite(f.raw_c, path_pd, path_dr, jitter, Nc, B, bkgd, m->white_bkgd, m->rgb_padding, m->sigma_bias, lc.rgb, lc.dist, lc.acc, lc.trans, lc.tb,
-                            Nf > 0 ? f.weights : nullptr, nullptr, level_mask_mode(m), level_mask_box(m), stream));
+  RNERF_TRY(composite_level(m, B, coarse, bkgd, lc, Nf > 0 ? f.weights : nullptr, stream));
   Level lf = lc;
   if (Nf > 0) {
     const float* u = u_override;
@@ -660,20 +660,33 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
     else { hipEvent_t e = fine_packed.e; fine_packed.e = nullptr; RNERF_TRY(wait_point(st, e)); }      // the fine level's operand stream (packed beside the coarse forward) and no more
     RNERF_TRY(rnerf_nerfmlp_forward_train(t.packed_f, prec, f.rows_pd, f.rows_dr, nullptr, S, B, f.raw_f, t.save_f, bwd, max_workgroups, stream));
     lf = level_of(t.level_f, B);
-    RNERF_TRY(rnerf_composite(f.raw_f, f.rows_pd, f.rows_dr, nullptr, S, B, bkgd, m->white_bkgd, m->rgb_padding, m->sigma_bias, lf.rgb, lf.dist, lf.acc, lf.trans,
-                              lf.tb, nullptr, nullptr, level_mask_mode(m), level_mask_box(m), stream));
-    if (m->bd_cut == 1) RNERF_TRY(bd_cut_pair(m, f.raw_f, f.rows_pd, f.rows_dr, S, B, bkgd, lf, f.tmp_level, f.tmp_level2, stream));
+    RNERF_TRY(composite_level(m, B, fine, bkgd, lf, nullptr, stream));
+    if (m->bd_cut == 1) RNERF_TRY(bd_cut_pair(m, fine, B, bkgd, lf, f.tmp_level, f.tmp_level2, stream));
   }
   // ---- loss reductions (train.py:89-92,105) ----
   RNERF_TRY(rnerf_loss_reduce(Nf > 0 ? lc.rgb : nullptr, lf.rgb, lf.trans, lf.tb, pixels, B, t.sums, stream));
   const double bg_on = (c->bg_weight > 0 && c->annealed_alpha > 0) ? 1.0 : 0.0;
   const double mse_scale = 2.0 / (3.0 * B);
   const double env_on = c->annealed_alpha > 0 ? 1.0 : 0.0;
-  if (!aux) RNERF_CHECK_HIP(hipMemsetAsync(grads, 0, (size_t)(n_theta + 8) * sizeof(float), st));
+  // ---- backward, last level first.  The steps are named once; the three schedules below list their enqueues in issue order. ----
+  // compositing + activations backward into d_raw; d_bkgd = t.d_all rows [0,B) (rows [B,B+M) are the env-map patch's, written by bkgd_bwd)
+  const LevelLoss last{pixels, lf.trans, lf.tb, t.sums, mse_scale, c->bg_weight * bg_on, 0}, under_fine{pixels, nullptr, nullptr, nullptr, mse_scale, 0.0, 1};
+  auto composite_bwd_fine = [&]() { return composite_level_backward(m, B, fine, bkgd, lf.rgb, last, t.d_raw, t.d_all, m->bd_cut == 1 ? 1 : level_mask_mode(m), stream); };
+  auto composite_bwd_coarse = [&](float* d_raw) { return composite_level_backward(m, B, coarse, bkgd, lc.rgb, Nf > 0 ? under_fine : last, d_raw, t.d_all, level_mask_mode(m), stream); };
+  // the NerfMLP backward of one level: transposed operand stream, dgrad (d_raw -> dy; zero_ref: it clears the row-scale reference of dy
+  // itself, allow_half: it may take 128-row tiles when they all fit one round), wgrad (dy -> the level's gradient segment)
+  struct MlpLevel { const float* theta; void *packed_bwd, *packed_fwd, *save; int64_t rows; float* grad; };
+  const MlpLevel mlp_c{th_c, t.packed_bwd, t.packed_c, t.save_c, (int64_t)Nc * B, g_c}, mlp_f{th_f, t.packed_bwd_f, t.packed_f, t.save_f, (int64_t)S * B, g_f};
+  auto pack_bwd = [&](const MlpLevel& l, void* s) { return rnerf_nerfmlp_pack_bwd(l.theta, bwd, l.packed_bwd, s); };
+  auto dgrad = [&](const MlpLevel& l, const float* d_raw, void* dy, bool zero_ref, bool allow_half, void* s) {
+    return nerfmlp_dgrad_impl(l.packed_bwd, l.packed_fwd, prec, bwd, l.save, d_raw, l.rows, dy, zero_ref, allow_half, (hipStream_t)s);
+  };
+  auto wgrad = [&](const MlpLevel& l, const void* dy, void* wgrad_ws, void* s) { return rnerf_nerfmlp_wgrad(prec, bwd, l.save, dy, l.rows, l.grad, wgrad_ws, s); };
   // The next batch's march on the side stream, forked from `stream` right before the LARGEST wgrad of the step (the fine level's when there
   // is one): the wgrad keeps 64 registers free on every SIMD (WGRAD_VGPRS in mlp.hip), so the march's waves are co-resident with it and the
   // whole march hides behind that HBM-paced kernel.
   auto march_next = [&]() -> int {
+    if (!next) return RNERF_OK;
     RNERF_CHECK_ARG(next->origins && next->viewdirs && next->path_pd && next->path_dr && next->side_stream, "rnerf_train_forward_backward: incomplete rnerf_prefetch");
     RNERF_CHECK_ARG((next->next_keys4 == nullptr) == (next->sample_nodes == nullptr), "rnerf_train_forward_backward: rnerf_prefetch needs both next_keys4 and sample_nodes or neither");
     RNERF_CHECK_ARG(!next->sample_nodes || Nf == 0, "rnerf_train_forward_backward: rnerf_prefetch.sample_nodes is for flat models (num_fine == 0) only");
@@ -684,73 +697,90 @@ extern "C" int rnerf_train_forward_backward(const rnerf_model* m, const rnerf_tr
     return rnerf_march_sparse(m->table, &m->grid, next->origins, next->viewdirs, B, m->near, m->far, N, next->path_pd, next->path_dr,
                               next->sample_nodes, m->num_path, next->side_stream);
   };
-  // ---- backward, last level first ----
-  if (aux) RNERF_TRY(rnerf_join(stream, aux));
-  float* d_first = t.d_all;                      // rows [0,B): d loss / d bkgd of the rays; rows [B,B+M): the env-map patch
-  // Hierarchical models with an aux stream (round 4): the two levels' backward passes are independent once both compositing backwards have
-  // run (the coarse one accumulates d bkgd on top of the fine one's), so the coarse level's dgrad + wgrad go to the aux stream, with buffers
-  // of their own, BESIDE the fine level's.  Each NerfMLP kernel owns whole CUs, so the two never share one — but whenever one level's
-  // persistent grid leaves CUs idle (all of a small batch: 512 rays x (64 + 128) samples are 128 + 384 row tiles on 256 CUs) the other
-  // level's workgroups take them: 2 rounds of tiles instead of 1 + 2 at that size.  Only for batches whose two levels together fit two
-  // rounds: beyond that the kernels' static tile striding is delayed on the CUs the other level took first and the step gets SLOWER
-  // (profiles/r04/levels_side_by_side.txt: 512 rays 2.28 -> 2.18 ms, 128 rays 1.50 -> 1.33; 1024 rays 3.36 -> 3.45, 4096 rays 11.9 -> 12.4).
-  const bool split_levels = levels_side_by_side(m, c, B);
-  float* d_raw_c = split_levels ? t.d_raw_c : t.d_raw;
-  void* dy_c = split_levels ? t.dy_c : t.dy;
-  if (Nf > 0) {
-    RNERF_TRY(rnerf_composite_backward(f.raw_f, f.rows_pd, f.rows_dr, nullptr, S, B, bkgd, m->rgb_padding, m->sigma_bias, lf.rgb, pixels, lf.trans, lf.tb, t.sums,
-                                       mse_scale, c->bg_weight * bg_on, t.d_raw, d_first, 0, m->white_bkgd, m->bd_cut == 1 ? 1 : level_mask_mode(m), m->bd_cut ? m->bd_cut_bbox : nullptr, stream));
-    if (split_levels) {
-      RNERF_TRY(rnerf_composite_backward(f.raw_c, path_pd, path_dr, jitter, Nc, B, bkgd, m->rgb_padding, m->sigma_bias, lc.rgb, pixels, nullptr, nullptr, nullptr,
-                                         mse_scale, 0.0, d_raw_c, d_first, 1, m->white_bkgd, level_mask_mode(m), level_mask_box(m), stream));
-      RNERF_TRY(rnerf_fork(stream, aux));
-      // d loss / d background is final (both compositing backwards have run): its whole backward goes beside the NerfMLP chains, in front
-      // of the coarse level's on the aux stream
-      if (smooth) RNERF_TRY(rnerf_env_smooth_backward(rgb_env, ps, c->bg_smooth_weight * env_on, t.d_all + (size_t)3 * B, t.env_sum, aux));
-      RNERF_TRY(rnerf_bkgd_backward(th_b, t.save_bk, t.d_all, (int64_t)B + M, m->rgb_padding, t.dy_bk, g_b, nullptr, aux));
-      RNERF_TRY(nerfmlp_dgrad_impl(t.packed_bwd, t.packed_c, prec, bwd, t.save_c, d_raw_c, (int64_t)Nc * B, dy_c, !pre_zeroed, false, (hipStream_t)aux));
-      RNERF_TRY(rnerf_nerfmlp_wgrad(prec, bwd, t.save_c, dy_c, (int64_t)Nc * B, g_c, t.wgrad_ws_c, aux));
+  // What does not touch the NerfMLP gradients: the env-map term + the background MLP's whole backward (d_all / save_bk / rgb_env -> g_b, env_sum,
+  // dy_bk) and the statistics (sums / env_sum -> stats8; th: sum theta^2 is taken here, nullptr: the head of the step took it on the aux stream)
+  auto bkgd_bwd = [&](void* s) -> int {
+    if (smooth) RNERF_TRY(rnerf_env_smooth_backward(rgb_env, ps, c->bg_smooth_weight * env_on, t.d_all + (size_t)3 * B, t.env_sum, s));
+    return rnerf_bkgd_backward(th_b, t.save_bk, t.d_all, (int64_t)B + M, m->rgb_padding, t.dy_bk, g_b, nullptr, s);
+  };
+  auto train_stats = [&](const float* th, void* s) {
+    return rnerf_train_stats(t.sums, B, Nf > 0, c->bg_weight * bg_on, smooth ? t.env_sum : nullptr, ps, env_on, th, n_theta, c->frozen_sq, n_theta + c->frozen_count, stats8, s);
+  };
+  // the NerfMLP gradient segments are final on `stream`: the caller's collective may start
+  auto grads_ready = [&]() { return c->grads_stream ? rnerf_fork(stream, c->grads_stream) : RNERF_OK; };
+
+  if (!aux) {
+    // ---- one stream, nothing cleared or packed ahead: the gradients are zeroed here, every level packs its transposed stream, every dgrad clears its reference
+    RNERF_CHECK_HIP(hipMemsetAsync(grads, 0, (size_t)(n_theta + 8) * sizeof(float), st));
+    if (Nf > 0) {
+      RNERF_TRY(composite_bwd_fine());
+      RNERF_TRY(pack_bwd(mlp_f, stream));
+      RNERF_TRY(dgrad(mlp_f, t.d_raw, t.dy, true, true, stream));
+      RNERF_TRY(march_next());
+      RNERF_TRY(wgrad(mlp_f, t.dy, t.wgrad_ws, stream));
     }
-    if (!aux) RNERF_TRY(rnerf_nerfmlp_pack_bwd(th_f, bwd, t.packed_bwd_f, stream));
-    RNERF_TRY(nerfmlp_dgrad_impl(t.packed_bwd_f, t.packed_f, prec, bwd, t.save_f, t.d_raw, (int64_t)S * B, t.dy, !pre_zeroed, !split_levels, st));
-    if (next) RNERF_TRY(march_next());
-    RNERF_TRY(rnerf_nerfmlp_wgrad(prec, bwd, t.save_f, t.dy, (int64_t)S * B, g_f, t.wgrad_ws, stream));
-    if (split_levels)
-      RNERF_TRY(rnerf_join(stream, aux));
-    else
-      RNERF_TRY(rnerf_composite_backward(f.raw_c, path_pd, path_dr, jitter, Nc, B, bkgd, m->rgb_padding, m->sigma_bias, lc.rgb, pixels, nullptr, nullptr, nullptr,
-                                         mse_scale, 0.0, t.d_raw, d_first, 1, m->white_bkgd, level_mask_mode(m), level_mask_box(m), stream));
-  } else {
-    RNERF_TRY(rnerf_composite_backward(f.raw_c, path_pd, path_dr, jitter, Nc, B, bkgd, m->rgb_padding, m->sigma_bias, lf.rgb, pixels, lf.trans, lf.tb, t.sums,
-                                       mse_scale, c->bg_weight * bg_on, t.d_raw, d_first, 0, m->white_bkgd, level_mask_mode(m), level_mask_box(m), stream));
+    RNERF_TRY(composite_bwd_coarse(t.d_raw));
+    RNERF_TRY(pack_bwd(mlp_c, stream));
+    RNERF_TRY(dgrad(mlp_c, t.d_raw, t.dy, true, true, stream));
+    if (Nf == 0) RNERF_TRY(march_next());
+    RNERF_TRY(wgrad(mlp_c, t.dy, t.wgrad_ws, stream));
+    RNERF_TRY(grads_ready());
+    RNERF_TRY(bkgd_bwd(stream));
+    RNERF_TRY(train_stats(theta, stream));
+    return RNERF_OK;
   }
-  if (!aux) RNERF_TRY(rnerf_nerfmlp_pack_bwd(th_c, bwd, t.packed_bwd, stream));
-  if (!split_levels)      // (a hierarchical model's coarse dgrad is the SECOND writer of t.dy here: it clears its own reference)
-    RNERF_TRY(nerfmlp_dgrad_impl(t.packed_bwd, t.packed_c, prec, bwd, t.save_c, t.d_raw, (int64_t)Nc * B, t.dy, !(pre_zeroed && Nf == 0), true, st));
-  if (next && Nf == 0) RNERF_TRY(march_next());
-  // The tail of the step that does not touch the NerfMLP gradients: the env-map term, the background MLP's whole backward and the
-  // statistics read d_all / save_bk / rgb_env / sums only and write g_b, env_sum, dy_bk and stats8.  With an aux stream (idle since the
-  // head of the step) they are queued there behind the last DGRAD launch — not behind the compositing backward: small workgroups that
-  // take CUs ahead of the persistent dgrad delay its static tile striding on every CU they sat on (profiles/r04/levels_side_by_side.txt)
-  // — so they become ready together with the last wgrad and run as co-resident waves beside it, like the march, instead of behind it:
-  // 0.13 ms of dependent small launches leave the end of the step, the wgrad pays 0.05 ms for the company (profiles/step_chain/).
-  // Order of execution only: no kernel and no operand changes.
-  const bool tail_on_aux = aux && !split_levels;
-  void* tail = tail_on_aux ? aux : stream;
-  if (tail_on_aux) RNERF_TRY(rnerf_fork(stream, aux));
-  if (!split_levels && !tail_on_aux) RNERF_TRY(rnerf_nerfmlp_wgrad(prec, bwd, t.save_c, t.dy, (int64_t)Nc * B, g_c, t.wgrad_ws, stream));
-  if (!tail_on_aux && c->grads_stream) RNERF_TRY(rnerf_fork(stream, c->grads_stream));      // the NerfMLP gradient segments are final: the caller's collective may start
-  if (!split_levels) {
-    if (smooth) RNERF_TRY(rnerf_env_smooth_backward(rgb_env, ps, c->bg_smooth_weight * env_on, t.d_all + (size_t)3 * B, t.env_sum, tail));
-    RNERF_TRY(rnerf_bkgd_backward(th_b, t.save_bk, t.d_all, (int64_t)B + M, m->rgb_padding, t.dy_bk, g_b, nullptr, tail));
-  }
-  RNERF_TRY(rnerf_train_stats(t.sums, B, Nf > 0, c->bg_weight * bg_on, smooth ? t.env_sum : nullptr, ps, env_on, aux ? nullptr : theta, n_theta, c->frozen_sq,
-                              n_theta + c->frozen_count, stats8, tail));
-  if (tail_on_aux) {
-    RNERF_TRY(rnerf_nerfmlp_wgrad(prec, bwd, t.save_c, t.dy, (int64_t)Nc * B, g_c, t.wgrad_ws, stream));
-    if (c->grads_stream) RNERF_TRY(rnerf_fork(stream, c->grads_stream));
+  // With an aux stream the head of the step has packed the backward's streams, zeroed the gradients, cleared the row-scale reference of the
+  // FIRST writer of every dY buffer and taken sum theta^2 there: joined here.
+  RNERF_TRY(rnerf_join(stream, aux));
+  if (!levels_side_by_side(m, c, B)) {
+    // ---- aux stream, the levels one after another (flat models; hierarchical ones beyond two rounds of row tiles).
+    if (Nf > 0) {
+      RNERF_TRY(composite_bwd_fine());
+      RNERF_TRY(dgrad(mlp_f, t.d_raw, t.dy, false, true, stream));
+      RNERF_TRY(march_next());
+      RNERF_TRY(wgrad(mlp_f, t.dy, t.wgrad_ws, stream));
+    }
+    RNERF_TRY(composite_bwd_coarse(t.d_raw));
+    // (a hierarchical model's coarse dgrad is the SECOND writer of t.dy here: it clears its own reference; a flat model's is the first)
+    RNERF_TRY(dgrad(mlp_c, t.d_raw, t.dy, Nf > 0, true, stream));
+    if (Nf == 0) RNERF_TRY(march_next());
+    // The tail of the step that does not touch the NerfMLP gradients (bkgd_bwd, train_stats).  The aux stream has been idle since the
+    // head of the step: they are queued there behind the last DGRAD launch — not behind the compositing backward: small workgroups that
+    // take CUs ahead of the persistent dgrad delay its static tile striding on every CU they sat on (profiles/r04/levels_side_by_side.txt)
+    // — so they become ready together with the last wgrad and run as co-resident waves beside it, like the march, instead of behind it:
+    // 0.13 ms of dependent small launches leave the end of the step, the wgrad pays 0.05 ms for the company (profiles/step_chain/).
+    // Order of execution only: no kernel and no operand changes.
+    RNERF_TRY(rnerf_fork(stream, aux));
+    RNERF_TRY(bkgd_bwd(aux));
+    RNERF_TRY(train_stats(nullptr, aux));
+    RNERF_TRY(wgrad(mlp_c, t.dy, t.wgrad_ws, stream));
+    RNERF_TRY(grads_ready());
     RNERF_TRY(rnerf_join(stream, aux));      // g_b and stats8 are final for whatever the caller queues on `stream` (its second all-reduce, the optimiser)
+    return RNERF_OK;
   }
+  // ---- aux stream, the two levels side by side (round 4): the two levels' backward passes are independent once both compositing backwards
+  // have run (the coarse one accumulates d bkgd on top of the fine one's), so the coarse level's dgrad + wgrad go to the aux stream, with
+  // buffers of their own (d_raw_c, dy_c, wgrad_ws_c), BESIDE the fine level's.  Each NerfMLP kernel owns whole CUs, so the two never share
+  // one — but whenever one level's persistent grid leaves CUs idle (all of a small batch: 512 rays x (64 + 128) samples are 128 + 384 row
+  // tiles on 256 CUs) the other level's workgroups take them: 2 rounds of tiles instead of 1 + 2 at that size.  Only for batches whose two
+  // levels together fit two rounds (levels_side_by_side): beyond that the kernels' static tile striding is delayed on the CUs the other
+  // level took first and the step gets SLOWER
+  // (profiles/r04/levels_side_by_side.txt: 512 rays 2.28 -> 2.18 ms, 128 rays 1.50 -> 1.33; 1024 rays 3.36 -> 3.45, 4096 rays 11.9 -> 12.4).
+  // Both dgrads are the first writers of their dY buffers (cleared at the head) and keep their 256-row tiles (allow_half = false).
+  RNERF_TRY(composite_bwd_fine());
+  RNERF_TRY(composite_bwd_coarse(t.d_raw_c));
+  RNERF_TRY(rnerf_fork(stream, aux));
+  // d loss / d background is final (both compositing backwards have run): its whole backward goes beside the NerfMLP chains, in front
+  // of the coarse level's on the aux stream
+  RNERF_TRY(bkgd_bwd(aux));
+  RNERF_TRY(dgrad(mlp_c, t.d_raw_c, t.dy_c, false, false, aux));
+  RNERF_TRY(wgrad(mlp_c, t.dy_c, t.wgrad_ws_c, aux));
+  RNERF_TRY(dgrad(mlp_f, t.d_raw, t.dy, false, false, stream));
+  RNERF_TRY(march_next());
+  RNERF_TRY(wgrad(mlp_f, t.dy, t.wgrad_ws, stream));
+  RNERF_TRY(rnerf_join(stream, aux));
+  RNERF_TRY(grads_ready());
+  RNERF_TRY(train_stats(nullptr, stream));
   return RNERF_OK;
 }
 

@@ -19,14 +19,13 @@ With more than one rank the step is two graphs around the gradient all-reduce (R
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Any, Dict, Optional
 
 import numpy as np
 import torch
 
 from . import _lib, distributed, ops
-from .train import TrainState, _bump, adam_cfg, frozen_sq_of, train_cfg
+from .train import TrainState, _bump, _issue_adam_update, adam_cfg, frozen_sq_of, stats_of, train_cfg
 from .utils import Rays, Stats
 
 
@@ -144,12 +143,7 @@ class GraphTrainStep:
                    "rnerf_train_forward_backward")
 
     def _issue_back(self) -> None:
-        s = self.state
-        fs = frozen_sq_of(s, s.variables)
-        frozen = s.variables["flat"].get("so3_mlp") if fs[1] > 0 else None
-        _lib.check(self.lib.rnerf_adam_update_fused(C.byref(self.a), s.theta.data_ptr(), s.mu.data_ptr(), s.nu.data_ptr(), s.grads.data_ptr(), s.theta.numel(),
-                                                    _lib.ptr(frozen), fs[1], s.step_dev.data_ptr(), s.adam_scratch.data_ptr(), None, self.main.cuda_stream),
-                   "rnerf_adam_update_fused")
+        _issue_adam_update(self.state, self.a, None, self.main.cuda_stream)
 
     def _capture(self, slot: int):
         lib, st, sd = self.lib, self.main.cuda_stream, self.side.cuda_stream
@@ -218,12 +212,7 @@ class GraphTrainStep:
         torch.cuda.current_stream().wait_stream(self.main)
         if self.prefetch:
             self.slot = 1 - slot
-        n = s.theta.numel()
-        s8 = s.grads[n:]
-        two = self.model.num_fine_samples > 0
-        return Stats(loss=s8[0], psnr=s8[6], loss_c=s8[1], psnr_c=(s8[7] if two else 0.0), weight_l2=s8[4], loss_sp=0.0, loss_nrm=0.0,
-                     annealing_rate=self.annealed, coarse_alpha_target=0.0, fine_alpha_target=0.0, loss_bg=s8[2],
-                     loss_bg_c=0.0, loss_bg_smooth=s8[3])
+        return stats_of(s.grads[s.theta.numel():], self.model.num_fine_samples > 0, self.annealed)
 
     def synchronize(self) -> None:
         self.main.synchronize()

@@ -11,7 +11,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 import weakref
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
@@ -150,14 +149,16 @@ class NerfModel:
         # VoxMLP.setup: data = concat([grid, grad]) (rnerf/ior_utils.py:161) — built once on the device
         self.table = ops.grid_build_table(g, self.spec)
         self._packed: Dict[str, Tuple[Any, int, torch.Tensor]] = {}
-        self._jit_cache: Dict[bytes, torch.Tensor] = {}
+        self._packed_bwd: Dict[str, Tuple[Any, int, torch.Tensor, int]] = {}      # the dgrad streams (train._bwd_packed)
+        self._jit_cache: Dict[bytes, Tuple[torch.Tensor, torch.Tensor]] = {}      # _pinned_upload entries: (pinned source, device tensor)
         self._u_lin: Optional[torch.Tensor] = None
         self._side: Optional[torch.cuda.Stream] = None
+        self._tail: Optional[torch.cuda.Stream] = None
         self._mlp_wg_limit = 0
         # whole_path: apply() goes through rnerf_forward (one C call per batch); False keeps the stage-by-stage host sequence (tests / taps)
         self.whole_path = True
         self._ws: Dict[Tuple[str, int], torch.Tensor] = {}
-        self._key_cache: Dict[bytes, torch.Tensor] = {}
+        self._key_cache: Dict[bytes, Tuple[torch.Tensor, torch.Tensor]] = {}
 
     def table_reference(self) -> torch.Tensor:
         """The (n, grad n) table in the reference's order [G^3, 4] whatever layout the kernels use (for the oracle and the tests)."""
@@ -207,21 +208,19 @@ class NerfModel:
             raise ValueError("jitter must be int[N_c] with values in [0, N_c*P)")
         if np.any(np.diff(j) <= 0):
             raise ValueError("jitter must be strictly increasing")
-        k = j.tobytes()
-        t = self._jit_cache.get(k)
-        if t is None:
-            if len(self._jit_cache) > 64:
-                self._jit_cache.clear()
-            # pinned staging + asynchronous copy: a pageable H2D copy would block the host until the stream drains, i.e. once
-            # per training step (the jitter is redrawn every step); the cache keeps the pinned buffer alive until it is evicted
-            pin = torch.from_numpy(j).pin_memory()
-            t = pin.to(self.device, non_blocking=True)
-            self._jit_cache[k] = t
-            self._jit_pins = getattr(self, "_jit_pins", {})
-            if len(self._jit_pins) > 64:
-                self._jit_pins.clear()
-            self._jit_pins[k] = pin
-        return t
+        return self._pinned_upload(self._jit_cache, j)
+
+    def _pinned_upload(self, cache: Dict[bytes, Tuple[torch.Tensor, torch.Tensor]], host: np.ndarray) -> torch.Tensor:
+        """A small host array as a device tensor, cached by value.  Pinned staging + asynchronous copy: a pageable H2D copy would block the host until
+        the stream drains, i.e. once per training step (the jitter is redrawn every step); the entry keeps the pinned buffer alive until evicted."""
+        b = host.tobytes()
+        ent = cache.get(b)
+        if ent is None:
+            if len(cache) > 64:
+                cache.clear()
+            pin = torch.from_numpy(host).pin_memory()
+            ent = cache[b] = (pin, pin.to(self.device, non_blocking=True))
+        return ent[1]
 
     def make_u(self, key, batch: int, randomized: bool):
         """The uniform draws of sorted_piecewise_constant_pdf (rnerf/model_utils.py:343-356), sample-major."""
@@ -316,7 +315,7 @@ class NerfModel:
 
     def tail_stream(self) -> torch.cuda.Stream:
         """The stream rnerf_train_forward_backward uses for work that is independent of the NerfMLP backward (rnerf_train_cfg.aux_stream)."""
-        if getattr(self, "_tail", None) is None:
+        if self._tail is None:
             self._tail = shared_stream(self.device, "tail")
         return self._tail
 
@@ -368,15 +367,7 @@ class NerfModel:
     def _keys_dev(self, *keys) -> torch.Tensor:
         """jax.random keys as a device uint32 vector (pinned staging, asynchronous copy, cached by value like the jitter)."""
         k = np.ascontiguousarray(np.concatenate([np.asarray(x, np.uint32).reshape(2) for x in keys]))
-        b = k.tobytes()
-        t = self._key_cache.get(b)
-        if t is None:
-            if len(self._key_cache) > 64:
-                self._key_cache.clear()
-            pin = torch.from_numpy(k.view(np.int32)).pin_memory()
-            t = (pin, pin.to(self.device, non_blocking=True))
-            self._key_cache[b] = t
-        return t[1]
+        return self._pinned_upload(self._key_cache, k.view(np.int32))
 
     def _forward_whole(self, variables, rng_0, rng_1, rays: Rays, randomized: bool, jitter, u_fine, path):
         """NerfModel.__call__ through rnerf_forward: the keys go to the device, every stage is sequenced there."""
@@ -408,15 +399,7 @@ class NerfModel:
                     u = torch.empty((Nf, B), dtype=torch.float32, device=self.device)
                     _lib.check(lib.rnerf_stratified_u_dev(key_u.data_ptr(), B, Nf, u.data_ptr(), st), "rnerf_stratified_u_dev")
                 per_ray = 1
-        pd = dr = None
-        if path is not None:
-            path.need_dense("NerfModel.apply")
-            if path.batch != B:
-                raise ValueError("path handle was marched for a different batch size")
-            cur = torch.cuda.current_stream()
-            cur.wait_event(path.event)
-            pd, dr = path.pd, path.dr
-            pd.record_stream(cur); dr.record_stream(cur)
+        pd, dr = path.adopt(B) if path is not None else (None, None)
         ws = self._workspace("fwd", lib.rnerf_forward_workspace_bytes(C.byref(m), B))
         out_c = torch.empty(_lib.LEVEL_FLOATS * B, dtype=torch.float32, device=self.device)
         out_f = torch.empty(_lib.LEVEL_FLOATS * B, dtype=torch.float32, device=self.device) if Nf > 0 else None
@@ -460,15 +443,7 @@ class NerfModel:
         sparsity = self.use_online_sparsity and (ctx is None or (bool(ctx.get("loss_sp")) and not self.stage.startswith("all")))
         want_ior = sparsity or (taps is not None and not (ctx is not None and self.stage.startswith("all")))
         if path is not None:
-            path.need_dense("NerfModel.apply")
-            if path.batch != B:
-                raise ValueError("path handle was marched for a different batch size")
-            cur = torch.cuda.current_stream()
-            cur.wait_event(path.event)
-            path_pd, path_dr, path_ior = path.pd, path.dr, path.ior
-            for t in (path_pd, path_dr, path_ior):
-                if t is not None:
-                    t.record_stream(cur)
+            (path_pd, path_dr), path_ior = path.adopt(B), path.ior
             if want_ior and path_ior is None:
                 raise ValueError("path handle lacks the IoR record (prefetch it from a model with the same options)")
         elif self.stage.startswith("all") and ctx is not None:                            # training: the march also records what its adjoint needs
@@ -692,6 +667,20 @@ class PathHandle:
         self._dr[rest] = dr[rest]
         self._pd.record_stream(cur); self._dr.record_stream(cur)
         self.sparse = False
+
+    def adopt(self, batch: int, raw: bool = False, who: str = "NerfModel.apply"):
+        """Hand the record of `batch` rays to the current stream -> (pd, dr): it waits for the march and is recorded as a reader of the buffers
+        (ior / jitter too, where present).  raw=True: as the march left them, the only way to read a sparse handle (refused otherwise)."""
+        if self.batch != batch:
+            raise ValueError("path handle was marched for a different batch size")
+        if not raw:
+            self.need_dense(who)
+        cur = torch.cuda.current_stream()
+        cur.wait_event(self.event)
+        for t in (self._pd, self._dr, self.ior, self.jitter):
+            if t is not None:
+                t.record_stream(cur)
+        return self._pd, self._dr                  # (a dense handle's pd / dr; a sparse one's would complete it first)
 
     def need_dense(self, who: str) -> None:
         if self.sparse:

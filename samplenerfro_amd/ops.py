@@ -6,7 +6,6 @@ Layouts: "sample-major" arrays are [S, B, ...] tensors (sample/node index first,
 from __future__ import annotations
 
 import ctypes as C
-import os
 import weakref
 from typing import Optional, Tuple
 
@@ -27,12 +26,18 @@ def _chk(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
 _workspaces: dict = {}            # (query name, device index, stream) -> uint8 tensor: the workspaces of workspace(..., keep_for=stream)
 
 
+def _size(name: str, *args) -> int:
+    """What the size query `lib.<name>(*args)` answers (rnerf_*_bytes / rnerf_*_floats); 0 is its error."""
+    n = getattr(_lib.load(), name)(*args)
+    if n == 0:
+        check(-1, name)
+    return n
+
+
 def workspace(name: str, *args, device, keep_for: Optional[int] = None) -> torch.Tensor:
     """A uint8 tensor on `device` of at least the bytes `lib.<name>(*args)` answers (an rnerf_*_workspace_bytes query; 0 is its error).
     keep_for: a stream handle — the buffer is kept for that device and stream and grown when a later call needs more."""
-    nb = getattr(_lib.load(), name)(*args)
-    if nb == 0:
-        check(-1, name)
+    nb = _size(name, *args)
     if keep_for is None:
         return torch.empty(nb, dtype=torch.uint8, device=device)
     key = (name, torch.device(device).index, keep_for)
@@ -87,9 +92,7 @@ def grid_build_table(grid: torch.Tensor, spec: Grid) -> torch.Tensor:
     n = spec.dims[0] * spec.dims[1] * spec.dims[2]
     if g.numel() != n:
         raise _lib.RnerfError(f"grid has {g.numel()} voxels, spec says {n}")
-    nf = lib.rnerf_grid_table_floats(C.byref(spec))
-    if nf == 0:
-        check(-1, "rnerf_grid_table_floats")
+    nf = _size("rnerf_grid_table_floats", C.byref(spec))
     table = torch.empty((nf // 4, 4), dtype=torch.float32, device=g.device)      # in spec.layout (bricks pad odd dimensions)
     check(lib.rnerf_grid_build_table(ptr(g), ptr(table), C.byref(spec), current_stream()), "rnerf_grid_build_table")
     return table
@@ -162,9 +165,7 @@ def nerfmlp_pack(params_flat: torch.Tensor, precision: int, out: Optional[torch.
     p = _chk(params_flat, "params_flat")
     if p.numel() != _lib.NERFMLP_PARAMS:
         raise _lib.RnerfError(f"NerfMLP flat params must have {_lib.NERFMLP_PARAMS} floats, got {p.numel()}")
-    nbytes = lib.rnerf_nerfmlp_packed_bytes(int(precision))
-    if nbytes == 0:
-        check(-1, "rnerf_nerfmlp_packed_bytes")
+    nbytes = _size("rnerf_nerfmlp_packed_bytes", int(precision))
     if out is None:
         out = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
     check(lib.rnerf_nerfmlp_pack(ptr(p), int(precision), ptr(out), current_stream()), "rnerf_nerfmlp_pack")
@@ -405,11 +406,7 @@ def sample_batch(camtoworlds: torch.Tensor, images: Optional[torch.Tensor], ray_
     if bad_count is None:
         bad_count = torch.zeros(1, dtype=torch.int32, device=dev)
     pc = 0.5 if pixel_center else 0.0
-    if cam_mat is None:
-        cam = (0, float(focal), float(focal), W * 0.5, H * 0.5)
-    else:
-        cam = (1, float(cam_mat[0][0]), float(cam_mat[1][1]), float(cam_mat[0][2]), float(cam_mat[1][2]))
-    check(lib.rnerf_sample_batch(ptr(c2w), n, cam[0], cam[1], cam[2], cam[3], cam[4], pc, int(W), int(H), ptr(images), ch, ptr(idx), B, ptr(o), ptr(d),
+    check(lib.rnerf_sample_batch(ptr(c2w), n, *camera_args(H, W, focal, cam_mat), pc, int(W), int(H), ptr(images), ch, ptr(idx), B, ptr(o), ptr(d),
                                  ptr(v), ptr(pix), ptr(bad_count), current_stream()), "rnerf_sample_batch")
     return o, d, v, pix
 
@@ -461,12 +458,16 @@ SHELL_ORDER = True
 SHELL_ORDER_COARSEN = 8
 
 
+def _shell_key(table: torch.Tensor, o: torch.Tensor, v: torch.Tensor, near: float, far: float, num_nodes: int):      # of _SHELL_CACHE
+    return (id(o), o._version, id(v), v._version, o.shape[0], int(num_nodes), table.data_ptr(), float(near), float(far))
+
+
 def _shell_order(table: torch.Tensor, spec: Grid, o: torch.Tensor, v: torch.Tensor, near: float, far: float, num_nodes: int):
     """int32 permutation that groups rays whose paths meet the boundary shell (|grad n| > 1e-3, where so3_mlp is evaluated) over the
     same node range.  The shell interval of a ray is read off a coarse pre-march without so3 (the so3 rotation and the step length are
     irrelevant for grouping); rays are results-independent, so the order changes no value."""
     # cached per ray batch (tensor objects + versions): evaluating repeatedly on the same rays pays the pre-march and the sort once
-    key = (id(o), o._version, id(v), v._version, o.shape[0], int(num_nodes), table.data_ptr(), float(near), float(far))
+    key = _shell_key(table, o, v, near, far, num_nodes)
     ent = _SHELL_CACHE.get(key)
     if ent is not None and ent[0]() is o and ent[1]() is v:
         if ent[3] is not None:      # computed ahead on another stream (prefetch_shell_order): this stream waits for it, once
@@ -497,7 +498,7 @@ def prefetch_shell_order(table: torch.Tensor, spec: Grid, origins: torch.Tensor,
     if not (SHELL_ORDER and origins.shape[0] > 16):
         return
     o = _chk(origins, "origins"); v = _chk(viewdirs, "viewdirs")
-    key = (id(o), o._version, id(v), v._version, o.shape[0], int(num_nodes), table.data_ptr(), float(near), float(far))
+    key = _shell_key(table, o, v, near, far, num_nodes)
     if key in _SHELL_CACHE:
         return
     stream.wait_stream(torch.cuda.current_stream())

@@ -22,7 +22,6 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
-import os
 import weakref
 from typing import Any, Dict, Optional
 
@@ -69,6 +68,7 @@ class TrainState:
         self._lag_count = 0
         self._lag_word = None          # address of the _lag_host slot the update of the step being issued writes its non-finite count to
         self._lag_word_written = False
+        self._split_ahead = None       # (rng, its split) made one step early for the next step's sparse path (_split3)
         self.last_retry_stats = None
 
     def nonfinite_grads(self) -> int:
@@ -171,7 +171,7 @@ class TrainState:
 
 def _bwd_packed(model: NerfModel, state: TrainState, name: str, backward: int) -> torch.Tensor:
     """The transposed (dgrad) weight stream of one NerfMLP, re-packed when the parameters (or the backward mode) changed."""
-    cache = model.__dict__.setdefault("_packed_bwd", {})
+    cache = model._packed_bwd
     flat = state.variables["flat"][name]
     ent = cache.get(name)
     if ent is None or ent[0]() is not flat or ent[1] != flat._version or ent[3] != backward:
@@ -297,22 +297,30 @@ def adam_cfg(state: TrainState, flags, lr_override: Optional[float] = None) -> "
     return a
 
 
+def stats_of(s8: torch.Tensor, two_levels: bool, annealed: float, loss_sp=0.0) -> Stats:
+    """The Stats of a step from the eight floats rnerf_train_stats left behind the gradients (views: no host synchronisation)."""
+    return Stats(loss=s8[0], psnr=s8[6], loss_c=s8[1], psnr_c=(s8[7] if two_levels else 0.0), weight_l2=s8[4], loss_sp=loss_sp, loss_nrm=0.0,
+                 annealing_rate=annealed, coarse_alpha_target=0.0, fine_alpha_target=0.0, loss_bg=s8[2], loss_bg_c=0.0, loss_bg_smooth=s8[3])
+
+
+def _issue_adam_update(state: TrainState, a: "_lib.AdamCfg", word: Optional[int], stream: int) -> None:
+    """rnerf_adam_update_fused (two dependent launches; rnerf_adam_update's bits); word: pinned host float for its non-finite count, or None."""
+    fs = frozen_sq_of(state, state.variables)
+    frozen = state.variables["flat"].get("so3_mlp") if fs[1] > 0 else None
+    _lib.check(_lib.load().rnerf_adam_update_fused(C.byref(a), state.theta.data_ptr(), state.mu.data_ptr(), state.nu.data_ptr(), state.grads.data_ptr(),
+                                                   state.theta.numel(), _lib.ptr(frozen), fs[1], state.step_dev.data_ptr(), state.adam_scratch.data_ptr(),
+                                                   word, stream), "rnerf_adam_update_fused")
+
+
 def _adam_update_on_device(state: TrainState, flags) -> None:
     """train.py:169-183 + optax.adam on the flat buffers as ONE C call (rnerf_adam_update): weight-decay gradient, value / norm clip, Adam
     with the reference's schedule from the device-resident step counter, and the non-finite guard (adam_cfg: an update that met an inf / NaN
     gradient entry writes nothing and is counted).  state.grads holds the (all-reduced) gradient of the data terms."""
-    lib = _lib.load()
     default_lr = state._lr_fn_default is state.lr_fn
     a = adam_cfg(state, flags, None if default_lr else float(state.lr_fn(state.step)))
     state.sync_step_counter()
-    fs = frozen_sq_of(state, state.variables)
-    frozen = state.variables["flat"].get("so3_mlp") if fs[1] > 0 else None
-    # two dependent launches (rnerf_adam_update_fused: rnerf_adam_update's bits); the lagged range retry's host word is written by the update itself
-    word = getattr(state, "_lag_word", None)
-    _lib.check(lib.rnerf_adam_update_fused(C.byref(a), state.theta.data_ptr(), state.mu.data_ptr(), state.nu.data_ptr(), state.grads.data_ptr(),
-                                           state.theta.numel(), _lib.ptr(frozen), fs[1], state.step_dev.data_ptr(), state.adam_scratch.data_ptr(),
-                                           word, _lib.current_stream()), "rnerf_adam_update_fused")
-    if word is not None:
+    _issue_adam_update(state, a, state._lag_word, _lib.current_stream())      # the lagged range retry's host word is written by the update itself
+    if state._lag_word is not None:
         state._lag_word_written = True
     state.step += 1
     state._step_dev_value = state.step
@@ -362,18 +370,11 @@ def _train_step_whole(model: NerfModel, rng, state: TrainState, batch, flags, ji
         # another one — the step marches its own rays, as without a handle
         path = None
     if path is not None:
-        if path.batch != B:
-            raise ValueError("path handle was marched for a different batch size")
-        cur = torch.cuda.current_stream()
-        cur.wait_event(path.event)
-        pd, dr = path.raw()                        # (as the march left them: path.pd / path.dr would complete a sparse record first)
-        pd.record_stream(cur); dr.record_stream(cur)
+        pd, dr = path.adopt(B, raw=True)           # (as the march left them: path.pd / path.dr would complete a sparse record first)
         if path.sparse:                            # the array the march recorded by IS the step's jitter (the same draw from the same key)
             jit = path.jitter
-            jit.record_stream(cur)
     ws = model._workspace("train", lib.rnerf_train_workspace_bytes(C.byref(m), C.byref(c), B))
     G = state.grads
-    n_theta = state.theta.numel()
     # the march of the NEXT step goes to the model's side stream, forked behind the last wgrad inside the call: it runs beside the
     # background-MLP backward, the loss tail, the all-reduce and the optimiser update
     nxt, next_path = None, None
@@ -385,7 +386,7 @@ def _train_step_whole(model: NerfModel, rng, state: TrainState, batch, flags, ji
     # jax.lax.pmean of gradients and stats (train.py:166-167).  With more than one rank the NerfMLP segments (95 % of the bytes) start their
     # all-reduce on a side stream the call orders behind the last wgrad; the background-MLP gradients and the stats (computed on the aux
     # stream beside that wgrad, joined inside the call) follow in a small second one.
-    comm = model.comm_stream() if (distributed.active() and hasattr(model, "comm_stream")) else None
+    comm = model.comm_stream() if distributed.active() else None
     if comm is not None:
         c = _lib.TrainCfg.from_buffer_copy(c)          # (train_cfg results may be shared: the stream is this call's)
         c.grads_stream = comm.cuda_stream
@@ -403,11 +404,7 @@ def _train_step_whole(model: NerfModel, rng, state: TrainState, batch, flags, ji
     else:
         distributed.allreduce_mean_([G])
     _adam_update_on_device(state, flags)
-    s8 = G[n_theta:]
-    two = model.num_fine_samples > 0
-    stats = Stats(loss=s8[0], psnr=s8[6], loss_c=s8[1], psnr_c=(s8[7] if two else 0.0), weight_l2=s8[4], loss_sp=0.0, loss_nrm=0.0,
-                  annealing_rate=annealed, coarse_alpha_target=0.0, fine_alpha_target=0.0, loss_bg=s8[2], loss_bg_c=0.0,
-                  loss_bg_smooth=s8[3])
+    stats = stats_of(G[state.theta.numel():], model.num_fine_samples > 0, annealed)
     state.next_path = next_path
     return state, stats, rng
 
@@ -620,10 +617,9 @@ def _train_step_once(model: NerfModel, rng, state: TrainState, batch: Dict[str, 
         raise NotImplementedError(f"train_step: unknown stage {flags.stage!r}")
     if all_stage and model.stage != flags.stage:
         raise ValueError("stage all*: build the model with the same stage (the march must evaluate so3_mlp)")
-    if flags.beta_weight > 0 or flags.sparsity_weight > 0:
-        pass        # both are multiplied by annealing_rate = 0.0 (train.py:156): no contribution to loss or gradient
-    noisy = getattr(model, "noise_std", None) is not None and bool(flags.randomized)      # the raw-sigma regulariser: drawn on the host, staged path
-    if not all_stage and taps is None and forward_taps is None and getattr(model, "whole_path", False) and not noisy:
+    # (flags.beta_weight / flags.sparsity_weight: both terms are multiplied by annealing_rate = 0.0 (train.py:156): no contribution to loss or gradient)
+    noisy = model.noise_std is not None and bool(flags.randomized)      # the raw-sigma regulariser: drawn on the host, staged path
+    if not all_stage and taps is None and forward_taps is None and model.whole_path and not noisy:
         # the product path: the whole forward + backward is ONE call into librnerf.so (rnerf_train_forward_backward), the update another
         # (rnerf_adam_update); what follows below is the same sequence stage by stage, with taps (parity tests, stage all*)
         return _train_step_whole(model, rng, state, batch, flags, jitter, u_fine, path, next_rays)
@@ -737,14 +733,14 @@ def _train_step_once(model: NerfModel, rng, state: TrainState, batch: Dict[str, 
     distributed.allreduce_mean_([G[n_big:]])
     distributed.allreduce_end_mean_(pending, G[:n_big])
     grads = G[:n_theta]
+    # train.py:153-160: Stats.loss_sp = sparsity_weight * annealing_rate * loss_sp with annealing_rate = 0.0 — the reference's number is 0.0
+    # whatever the term's value (models.py:351-357 keeps it finite: safe_log, a denominator >= 1); the value itself is in taps["loss_sp"]
+    annealing_rate = 0.0
+    stats = stats_of(st, rgb_c is not None, annealed, loss_sp=flags.sparsity_weight * annealing_rate * _loss_sp)
     if taps is None and state.adam_scratch is not None:
         # nobody looks at the gradient: the product form of the update — one C call with the non-finite guard — instead of the tensor
         # arithmetic below (stage all*, the noise_std steps: the sequences the whole-path entry does not cover)
         _adam_update_on_device(state, flags)
-        annealing_rate = 0.0
-        stats = Stats(loss=st[0], psnr=st[6], loss_c=st[1], psnr_c=(st[7] if rgb_c is not None else 0.0),
-                      weight_l2=st[4], loss_sp=flags.sparsity_weight * annealing_rate * _loss_sp, loss_nrm=0.0, annealing_rate=annealed, coarse_alpha_target=0.0,
-                      fine_alpha_target=0.0, loss_bg=st[2], loss_bg_c=0.0, loss_bg_smooth=st[3])
         state.next_path = next_path
         return state, stats, rng
     if flags.weight_decay_mult > 0:      # d (weight_decay_mult * weight_l2) / d theta: identical on every rank, so it is added after the mean
@@ -771,11 +767,5 @@ def _train_step_once(model: NerfModel, rng, state: TrainState, batch: Dict[str, 
         state.step += 1
     else:
         state.apply_gradients(grads)
-    # train.py:153-160: Stats.loss_sp = sparsity_weight * annealing_rate * loss_sp with annealing_rate = 0.0 — the reference's number is 0.0
-    # whatever the term's value (models.py:351-357 keeps it finite: safe_log, a denominator >= 1); the value itself is in taps["loss_sp"]
-    annealing_rate = 0.0
-    stats = Stats(loss=st[0], psnr=st[6], loss_c=st[1], psnr_c=(st[7] if rgb_c is not None else 0.0),
-                  weight_l2=st[4], loss_sp=flags.sparsity_weight * annealing_rate * _loss_sp, loss_nrm=0.0, annealing_rate=annealed, coarse_alpha_target=0.0, fine_alpha_target=0.0,
-                  loss_bg=st[2], loss_bg_c=0.0, loss_bg_smooth=st[3])
     state.next_path = next_path
     return state, stats, rng

@@ -69,3 +69,14 @@ def test_a_sparse_handle_knows_its_key_and_refuses_dense_consumers():
     dense = PathHandle(None, None, None, None, 4)
     dense.need_dense("test")
     assert not dense.sparse and not dense.matches(key)
+
+
+def test_adopt_refuses_a_wrong_batch_and_a_sparse_handle_before_touching_a_stream():
+    """PathHandle.adopt: both refusals come before the wait on the handle's event (event=None here: touching it would raise something else)."""
+    from samplenerfro_amd.models import PathHandle
+    sparse = PathHandle(None, None, None, None, 4, sparse=True, jitter=None, key=prng.PRNGKey(3))
+    for h, raw in ((PathHandle(None, None, None, None, 4), False), (sparse, True)):
+        with pytest.raises(ValueError, match="path handle was marched for a different batch size"):
+            h.adopt(5, raw=raw)
+    with pytest.raises(ValueError, match="holds the records of its own jitter's nodes only"):
+        sparse.adopt(4)
