@@ -942,6 +942,41 @@ int rnerf_path_plot(const float* path_pd, const float* path_ior, int32_t num_nod
                     int32_t R, const double* panels /* HOST [P][2][4] */, int32_t P, int32_t size, const double* box /* HOST [6] */,
                     double floor_z, double grad_eps, void* workspace, uint8_t* out, void* stream);
 
+/* ---- Ground-truth renderer for synthetic refractive scenes (csrc/scene.hip).  Appended; RNERF_VERSION stays 4 --------------------------
+ * The image formation of the reference's `*_skydome-bkgd_no-partial-reflect_cycles` scenes, which is also what the model family represents:
+ * an eikonal march through the IoR grid, an environment that depends on the last bent direction only, a grey medium in front of it.
+ *
+ * rnerf_scene_trace: the march of rnerf_march without path records.  table, g, origins [B][3], viewdirs [B][3], near, far, num_nodes as
+ * there (both table layouts, the same size limits); every value of the recurrence is produced by the same individually rounded float32
+ * operations in the same order, the step being (float)((far - near) / (num_nodes - 1)), wherever the grid coordinates (p - nmin) / ndelta
+ * stay below 2^31 in magnitude (beyond, the cell fraction is taken from a saturated integer here and from floor(x) there).  Per ray:
+ *   exit_dir float[B][4] = (safe_l2_normalize(d_{N-1}), 0): the bits rnerf_march writes into path_dr[N-1];
+ *   counts int32[2][B]: [0] the number of nodes k in [0, N) with n(p_k) > (float)n_inside (strict; a NaN does not count), [1] the number of
+ *   refracting nodes by the predicate of rnerf_path_summary, sqrt((a a + b b) + c c) > (float)grad_eps with the root correctly rounded
+ *   and a NaN not refracting.
+ * One launch; nothing of size N B is allocated or written.  RNERF_ERR_ARG before any device work for null pointers, B < 1, num_nodes < 2,
+ * a NaN n_inside or grad_eps, a table or exit_dir that is not 16-byte aligned, a grid rnerf_march would refuse. */
+int rnerf_scene_trace(const float* table, const rnerf_grid* g, const float* origins, const float* viewdirs, int32_t B, double near, double far,
+                      int32_t num_nodes, double n_inside, double grad_eps, float* exit_dir, int32_t* counts, void* stream);
+
+/* rnerf_scene_shade: the image from traced sub-pixel rays.  exit_dir float[(H K) (W K)][4] and counts int32[2][(H K) (W K)] are those of
+ * the K times finer camera, row-major over (H K, W K); env float[6][E][E][3] is a cube map; albedo: HOST double[3], rounded to float.  One
+ * thread per output pixel, its K K sub-samples taken in ascending (row, column) order of the fine image; every operation is an
+ * individually rounded float32 operation unless stated, nothing is contracted.
+ *   Cube map, for a direction d: m = max(|dx|, |dy|, |dz|), ties going to x before y before z; face 0..5 = +x, -x, +y, -y, +z, -z by the
+ *   sign of that component; (s, t) = (a / m, b / m) with (a, b) = (y, z), (z, x), (x, y) on the x, y, z faces, no sign flips;
+ *   u = ((s + 1) 0.5) E - 0.5 clamped to [0, E - 1], v from t likewise; i0 = floor, i1 = min(i0 + 1, E - 1), weight w = u - i0; bilinear as
+ *   a (1 - w) + b w, along u in rows v0 and v1 and then along v, with env[face][v][u].  m == 0 and a direction with a NaN component give black, and so does
+ *   a NaN face coordinate (inf / inf: two infinite components, which the rule above leaves without a texel); one infinite component
+ *   looks up its face's centre.
+ *   Sub-sample: T = (float)exp(((-sigma) step_len) (double)counts[0]) in float64 (exactly 1 when sigma == 0); colour = T env + (1 - T) albedo.
+ *   Pixel: rgb float[H][W][3] = the sum of the K K colours in that order, from 0, times (float)(1.0 / (K K)) as one multiply; trans
+ *   float[H][W] = the same mean of T; mask uint8[H][W] = 255 if any sub-sample has counts[1] > 0, else 0.
+ * One launch, no atomics: the same bytes on every run.  RNERF_ERR_ARG before any device work for null pointers, H, W, K or E < 1,
+ * H K W K beyond int32, an exit_dir that is not 16-byte aligned. */
+int rnerf_scene_shade(const float* exit_dir, const int32_t* counts, int32_t H, int32_t W, int32_t K, const float* env, int32_t E, double step_len,
+                      double sigma, const double* albedo /* HOST [3] */, float* rgb, float* trans, uint8_t* mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

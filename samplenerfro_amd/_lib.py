@@ -207,6 +207,9 @@ SIGNATURES = {
     "rnerf_path_summary": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _dbl, _vp, _vp, _vp]),
     "rnerf_path_plot_workspace_bytes": (C.c_size_t, [_i32, _i32]),
     "rnerf_path_plot": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, C.POINTER(_dbl), _i32, _i32, C.POINTER(_dbl), _dbl, _dbl, _vp, _vp, _vp]),
+    # ground-truth renderer for synthetic refractive scenes (csrc/scene.hip)
+    "rnerf_scene_trace": (C.c_int, [_vp, _GP, _vp, _vp, _i32, _dbl, _dbl, _i32, _dbl, _dbl, _vp, _vp, _vp]),
+    "rnerf_scene_shade": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _dbl, _dbl, C.POINTER(_dbl), _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

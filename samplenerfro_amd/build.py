@@ -16,7 +16,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "librnerf.so")
 LIB_EXPERIMENTS = os.path.join(LIBDIR, "librnerf_experiments.so")
 LIB_UBENCH = os.path.join(LIBDIR, "librnerf_ubench.so")       # csrc/ubench/mfma_rate.hip: the measured MFMA ceiling bench.py quotes (not the product)
-SOURCES = ["grid.hip", "march.hip", "render.hip", "mlp.hip", "small_mlp.hip", "mlp_f32.hip", "bkgd16.hip", "pipeline.hip", "metrics.hip", "hull.hip", "mcubes.hip", "raster.hip", "vis.hip", "images.hip", "errmap.hip", "lpips.hip", "components.hip", "paths.hip"]
+SOURCES = ["grid.hip", "march.hip", "render.hip", "mlp.hip", "small_mlp.hip", "mlp_f32.hip", "bkgd16.hip", "pipeline.hip", "metrics.hip", "hull.hip", "mcubes.hip", "raster.hip", "vis.hip", "images.hip", "errmap.hip", "lpips.hip", "components.hip", "paths.hip", "scene.hip"]
 # -ffp-contract=off + correctly rounded div/sqrt: the march/lookup/resample kernels reproduce the reference's
 # individually rounded fp32 op order so that integer indices are bit-exact against the oracle.
 # -fno-slp-vectorize: a performance choice first — hipcc's SLP pass packs adjacent scalar fp32 ops into v_pk_{mul,add,fma}_f32, which beside

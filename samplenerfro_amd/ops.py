@@ -1078,3 +1078,49 @@ def path_plot(path_pd: torch.Tensor, path_ior: Optional[torch.Tensor], rays: tor
                                   bx.ctypes.data_as(dp) if bx is not None else None, float(floor_z), float(grad_eps), ptr(ws), ptr(out),
                                   torch.cuda.current_stream(dev).cuda_stream), "rnerf_path_plot")
     return out
+
+
+def scene_trace(table: torch.Tensor, spec: Grid, origins: torch.Tensor, viewdirs: torch.Tensor, near: float, far: float, num_nodes: int, *,
+                n_inside: float, grad_eps: float = 1e-3):
+    """rnerf_scene_trace: the march of `march` that keeps only where each ray ends up.  origins, viewdirs [B, 3] (or [..., 3], flattened) ->
+    (exit_dir float32 [B, 4] = the bits of march's path_dr[N - 1], counts int32 [2, B] = nodes with n > n_inside, refracting nodes by
+    path_summary's rule).  One launch on the current stream of the rays' device; nothing of size N x B exists."""
+    lib = _lib.load()
+    table = _chk(table, "table"); o = _chk(origins, "origins").reshape(-1, 3); d = _chk(viewdirs, "viewdirs").reshape(-1, 3)
+    B = int(o.shape[0])
+    if B < 1 or tuple(d.shape) != (B, 3) or d.device != o.device or table.device != o.device:
+        raise ValueError(f"scene_trace: need origins and viewdirs [B, 3] with B >= 1 on the table's device, got {tuple(o.shape)} and {tuple(d.shape)}")
+    dev = o.device
+    with torch.cuda.device(dev):
+        exit_dir = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        counts = torch.empty((2, B), dtype=torch.int32, device=dev)
+        check(lib.rnerf_scene_trace(ptr(table), C.byref(spec), ptr(o), ptr(d), B, float(near), float(far), int(num_nodes), float(n_inside),
+                                    float(grad_eps), ptr(exit_dir), ptr(counts), torch.cuda.current_stream(dev).cuda_stream), "rnerf_scene_trace")
+    return exit_dir, counts
+
+
+def scene_shade(exit_dir: torch.Tensor, counts: torch.Tensor, H: int, W: int, K: int, env: torch.Tensor, *, step_len: float, sigma: float = 0.0,
+                albedo=(0.0, 0.0, 0.0)):
+    """rnerf_scene_shade: the image of the traced rays of the K times finer camera (exit_dir [(H K) (W K), 4], counts [2, (H K) (W K)],
+    row-major over the fine image) in the cube map env float32 [6, E, E, 3] behind a grey medium of extinction sigma per unit length
+    (step_len: the march's step) and colour albedo -> (rgb float32 [H, W, 3], trans float32 [H, W], mask uint8 [H, W]).  One launch on the
+    current stream of exit_dir's device."""
+    lib = _lib.load()
+    H, W, K = int(H), int(W), int(K)
+    n = H * K * W * K
+    e = _chk(exit_dir, "exit_dir"); c = _chk(counts, "counts", torch.int32); env = _chk(env, "env")
+    if tuple(e.shape) != (n, 4) or tuple(c.shape) != (2, n):
+        raise ValueError(f"scene_shade: need exit_dir [{n}, 4] and counts [2, {n}] for a {H} x {W} image at K = {K}, got {tuple(e.shape)} and {tuple(c.shape)}")
+    if env.dim() != 4 or int(env.shape[0]) != 6 or env.shape[1] != env.shape[2] or int(env.shape[3]) != 3:
+        raise ValueError(f"scene_shade: env must be [6, E, E, 3], got {tuple(env.shape)}")
+    dev = e.device
+    if c.device != dev or env.device != dev:
+        raise ValueError(f"scene_shade: exit_dir, counts and env must be on one device, got {dev}, {c.device}, {env.device}")
+    alb = (C.c_double * 3)(*(float(v) for v in albedo))
+    with torch.cuda.device(dev):
+        rgb = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        trans = torch.empty((H, W), dtype=torch.float32, device=dev)
+        mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        check(lib.rnerf_scene_shade(ptr(e), ptr(c), H, W, K, ptr(env), int(env.shape[1]), float(step_len), float(sigma), alb, ptr(rgb), ptr(trans),
+                                    ptr(mask), torch.cuda.current_stream(dev).cuda_stream), "rnerf_scene_shade")
+    return rgb, trans, mask
